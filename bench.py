@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark: 64-bit coefficients/s for c = INTT(NTT(a) (.) b) on
-N = 2^16, 16 towers, batch 1024 per GPU (BASELINE.json configs[2]), with the
-pipeline's HBM- and VALU-roofline fractions and a CPU baseline on the host cores.
+N = 2^16, 16 towers, batch 1024 per GPU (BASELINE.json configs[2]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of
+the last timed step when --dump-outputs is given, and prints the result line
+(`value`, `ms_per_step`: one timed step).  --full adds, after the timed
+region, everything else the line can carry: the per-kernel times and the
+pipeline's HBM- and VALU-roofline fractions, the power sample, the spot
+check against the oracle, the secondary operations, configs[3] / [4] / [0],
+the PCIe-inclusive rate and a CPU baseline on the host cores.
 
 --gpus N > 1 without WORLD_SIZE in the environment starts N ranks itself
 (torch.distributed.run, one process per GPU) before anything touches the GPU;
 under an external launcher WORLD_SIZE must equal N.  Each rank runs its own
 batch (weak scaling, no data-path collective); the only collective is the
 RCCL evaluation-key broadcast at setup.  Secondary lines in
-the same JSON object: configs[3] (32 towers split over the ranks, strong
+the same JSON object under --full: configs[3] (32 towers split over the ranks, strong
 scaling), configs[4] (HYBRID key switching, one bounded sample), configs[0]
 (CPU-only add / Hadamard, poly-benchmark semantics).
 
@@ -39,6 +46,8 @@ SIMDS = 1024                   # 256 CUs x 4 SIMDs
 VALU_ISSUE_CEILING = 0.25      # wave64 VALU instructions per SIMD per cycle (4-cycle issue)
 REF_CPU_MS_1T = 41.1           # reference NTT+Hadamard+INTT, 2^16 x 16 towers, 1 thread
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_current.json")
+DUMP_MAX_WORDS = 1 << 20       # --dump-outputs: words per output (3 float64 arrays of 8 MiB each)
+DUMP_SEED = 0x5EED             # --dump-outputs: seed of the sample of a larger output
 
 
 def build_id() -> str:
@@ -114,10 +123,17 @@ def parse_args(argv=None):
     ap.add_argument("--log-n", type=int, default=16)
     ap.add_argument("--towers", type=int, default=16)
     ap.add_argument("--batch", type=int, default=1024, help="polynomials per GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="pipeline workload: after the timed steps also measure and check everything else the "
+                         "line carries (per-kernel times and roofline, power, oracle spot check, secondary "
+                         "operations, configs[3]/[4]/[0], PCIe and CPU legs); a plain run does none of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pipeline workload: after the timed steps write what the last one computed to "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of a large output)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle spot check")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline only: skip configs[3]/[4]/[0], PCIe and CPU legs (profiling passes)")
+                    help="--full: skip power, secondary operations, configs[3]/[4]/[0], PCIe and CPU legs")
     ap.add_argument("--workload", default="pipeline", choices=["pipeline", "keyswitch", "rescale", "bv_keyswitch"],
                     help="pipeline = the headline metric (configs[2]); keyswitch = configs[4] HYBRID "
                          "key switching as the main line; rescale / bv_keyswitch = callers outside SURVEY.md "
@@ -232,6 +248,9 @@ def main():
             print(json.dumps({"launch_check": True, "n_gpus": 1, "ranks": [0], "pids": [os.getpid()]}))
             return
         sys.exit(launch_check(args))
+    if args.dump_outputs and args.workload != "pipeline":
+        print("bench.py: --dump-outputs writes the pipeline workload's outputs only", file=sys.stderr)
+        sys.exit(2)
     if args.workload == "keyswitch":
         sys.exit(bench_keyswitch_main(args))
     if args.workload in ("rescale", "bv_keyswitch"):
@@ -328,6 +347,52 @@ def headline_config(shard_mode, world, log_n, T_total, B):
             "global_batch": B, "parallelism": f"tower-sharded x{world} (no data-path collective)"}
 
 
+def dump_sample_index(numel):
+    """--dump-outputs: the flat indices written of an output of `numel` words:
+    None (all of it) up to DUMP_MAX_WORDS, else DUMP_MAX_WORDS indices drawn
+    with a fixed seed (the same for every run and build), ascending."""
+    import numpy as np
+
+    if numel <= DUMP_MAX_WORDS:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, size=DUMP_MAX_WORDS, dtype=np.int64))
+
+
+def dump_arrays(name, words):
+    """--dump-outputs: the float64 arrays one output of uint64 residues becomes.
+    <name> holds the residues themselves (rounded to float64's 53 bits above
+    2^53), <name>_lo32 / <name>_hi32 their low and high 32 bits, which float64
+    holds exactly: residue = hi32 * 2^32 + lo32."""
+    import numpy as np
+
+    assert words.dtype == np.uint64
+    return {name: words.astype(np.float64), name + "_lo32": (words & np.uint64(0xFFFFFFFF)).astype(np.float64),
+            name + "_hi32": (words >> np.uint64(32)).astype(np.float64)}
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs DIR: every output tensor (int64 storage of uint64
+    residues, on the device) as DIR/<name>.npy, DIR/<name>_lo32.npy and
+    DIR/<name>_hi32.npy; whole and in its own shape when it has at most
+    DUMP_MAX_WORDS words, else the 1-D sample of dump_sample_index.  Returns
+    what was written, for the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        idx = dump_sample_index(t.numel())
+        sel = t if idx is None else t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        words = sel.cpu().numpy().view(np.uint64)
+        for fname, arr in dump_arrays(name, words).items():
+            np.save(os.path.join(dirname, fname + ".npy"), arr)
+            written[fname] = {"shape": list(arr.shape), "dtype": str(arr.dtype)}
+        written[name]["of_shape"] = list(t.shape)
+        written[name]["sampled"] = idx is not None
+    return written
+
+
 def bench_pipeline(args):
     import torch
     import torch.distributed as dist
@@ -390,60 +455,62 @@ def bench_pipeline(args):
     value = coeffs_per_step * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
 
-    # per-kernel durations with HIP events on the launch stream (separate pass)
-    kernels_ms = {}
-    reps = max(3, min(args.steps, 10))
-    for st in (0, 1, 2):
-        if log_n <= 12 and st != 1:
-            continue
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        plan.ntt_mul_intt_stage(0, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
-        plan.ntt_mul_intt_stage(1, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
-        ev0.record(stream)
-        for _ in range(reps):
-            plan.ntt_mul_intt_stage(st, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
-        ev1.record(stream)
-        ev1.synchronize()
-        kernels_ms[STAGE_NAMES[st]] = ev0.elapsed_time(ev1) / reps
+    # c is what the last timed step left: written before anything else runs on it
+    dumped = dump_outputs(args.dump_outputs, {"c": c}) if (args.dump_outputs and rank == 0) else None
 
-    roofline = make_roofline(pipe_ms, kernels_ms, coeffs_rank, log_n, T, B, ms_per_step=ms_per_step)
-    power = power_sample(step, pipe_ms, local) if (rank == 0 and not args.no_extras) else None
+    # everything below the timed region that takes runs of its own: --full only
+    kernels_ms, roofline, power, parity, secondary, extras = {}, None, None, None, None, {}
+    if args.full:
+        # per-kernel durations with HIP events on the launch stream (separate pass)
+        reps = max(3, min(args.steps, 10))
+        for st in (0, 1, 2):
+            if log_n <= 12 and st != 1:
+                continue
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            plan.ntt_mul_intt_stage(0, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
+            plan.ntt_mul_intt_stage(1, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
+            ev0.record(stream)
+            for _ in range(reps):
+                plan.ntt_mul_intt_stage(st, a.data_ptr(), b.data_ptr(), c.data_ptr(), B, sp)
+            ev1.record(stream)
+            ev1.synchronize()
+            kernels_ms[STAGE_NAMES[st]] = ev0.elapsed_time(ev1) / reps
 
-    # spot parity check against the oracle (two (batch, tower) rows)
-    parity = None
-    if not args.no_check and rank == 0:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import numpy as np
-        import oracle as O
+        roofline = make_roofline(pipe_ms, kernels_ms, coeffs_rank, log_n, T, B, ms_per_step=ms_per_step)
+        power = power_sample(step, pipe_ms, local) if (rank == 0 and not args.no_extras) else None
 
-        step()
-        torch.cuda.synchronize()
-        ok = True
-        for bi, ti in ((0, 0), (B - 1, T - 1)):
-            tb = O.Tables(n, [qs[ti]], [roots[ti]])
-            aa = a[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
-            bb = b[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
-            cc = c[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
-            want_a = O.splitmix_fill(n, qs[ti], O.U([0x5EED ^ ((b0 + bi) << 20) ^ ((t_start + ti) << 8) ^ 1]))
-            ok = ok and bool(np.array_equal(aa.reshape(-1), want_a))
-            ok = ok and bool(np.array_equal(cc, O.ntt_mul_intt(aa, bb, tb)))
-        parity = ok
+        # spot parity check against the oracle (two (batch, tower) rows)
+        if not args.no_check and rank == 0:
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import numpy as np
+            import oracle as O
 
-    secondary = None
-    if not args.no_extras:
-        secondary = secondary_ops(plan, a, b, c, B, T, n, stream)
-    del a, b, c
-    torch.cuda.empty_cache()
-    extras = {}
-    if not args.no_extras:
-        extras["configs3"] = bench_configs3(args, ctx, world, rank, dev)
-        extras["keyswitch"] = bench_keyswitch(args, ctx, world, rank, dev, steps=args.ks_steps, warmup=2,
-                                              with_stages=True)
-        if rank == 0 and world == 1:
-            extras["pcie_inclusive"] = (pcie_inclusive(plan, args.pcie_batch, args.pcie_chunks, dev)
-                                        if args.pcie_chunks > 0 else None)
-            extras["configs0"] = bench_configs0(ctx)
-            extras["cpu_baseline"] = cpu_baseline(args, qs, roots, log_n, T) if args.cpu_seconds > 0 else None
+            step()
+            torch.cuda.synchronize()
+            ok = True
+            for bi, ti in ((0, 0), (B - 1, T - 1)):
+                tb = O.Tables(n, [qs[ti]], [roots[ti]])
+                aa = a[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
+                bb = b[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
+                cc = c[bi, ti].cpu().numpy().view(np.uint64).reshape(1, 1, n)
+                want_a = O.splitmix_fill(n, qs[ti], O.U([0x5EED ^ ((b0 + bi) << 20) ^ ((t_start + ti) << 8) ^ 1]))
+                ok = ok and bool(np.array_equal(aa.reshape(-1), want_a))
+                ok = ok and bool(np.array_equal(cc, O.ntt_mul_intt(aa, bb, tb)))
+            parity = ok
+
+        if not args.no_extras:
+            secondary = secondary_ops(plan, a, b, c, B, T, n, stream)
+        del a, b, c
+        torch.cuda.empty_cache()
+        if not args.no_extras:
+            extras["configs3"] = bench_configs3(args, ctx, world, rank, dev)
+            extras["keyswitch"] = bench_keyswitch(args, ctx, world, rank, dev, steps=args.ks_steps, warmup=2,
+                                                  with_stages=True)
+            if rank == 0 and world == 1:
+                extras["pcie_inclusive"] = (pcie_inclusive(plan, args.pcie_batch, args.pcie_chunks, dev)
+                                            if args.pcie_chunks > 0 else None)
+                extras["configs0"] = bench_configs0(ctx)
+                extras["cpu_baseline"] = cpu_baseline(args, qs, roots, log_n, T) if args.cpu_seconds > 0 else None
 
     status = capi_status({"headline": bcast, "keyswitch": (extras.get("keyswitch") or {}).get("evalkey_broadcast")},
                          world)
@@ -457,6 +524,8 @@ def bench_pipeline(args):
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
+            "full": args.full,
+            "outputs": dumped,
             "scaling": "weak" if args.shard == "batch" else "strong",
             "vs_baseline": None,
             "dtype": "u64",

@@ -37,6 +37,50 @@ def test_world_size_mismatch_is_an_error():
     assert "must agree" in r.stderr
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    import bench
+
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    args = bench.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert args.full is True and args.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_is_for_the_pipeline_workload(tmp_path):
+    r = subprocess.run([sys.executable, BENCH, "--workload", "keyswitch", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120, env=_env())
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    assert not (tmp_path / "d").exists()
+
+
+def test_dump_arrays_hold_every_bit_and_the_sample_is_fixed():
+    """--dump-outputs: 60-bit residues do not fit float64's 53 bits, so each
+    output is also written as exact 32-bit halves; a large output is sampled
+    at indices that depend on nothing but its size."""
+    import numpy as np
+
+    import bench
+
+    words = np.array([0, 1, (1 << 32) - 1, 1 << 32, (1 << 53) + 1, (1 << 60) - 93, (1 << 64) - 1], dtype=np.uint64)
+    arrs = bench.dump_arrays("c", words.reshape(7, 1))
+    assert sorted(arrs) == ["c", "c_hi32", "c_lo32"]
+    assert all(a.dtype == np.float64 and a.shape == (7, 1) for a in arrs.values())
+    back = (arrs["c_hi32"].astype(np.uint64) << np.uint64(32)) | arrs["c_lo32"].astype(np.uint64)
+    assert np.array_equal(back.reshape(-1), words)
+    assert np.array_equal(arrs["c"].reshape(-1), words.astype(np.float64))
+
+    assert bench.dump_sample_index(bench.DUMP_MAX_WORDS) is None
+    numel = 1024 * 16 * 65536  # the headline output
+    idx = bench.dump_sample_index(numel)
+    assert idx.shape == (bench.DUMP_MAX_WORDS,) and idx.dtype == np.int64
+    assert idx[0] >= 0 and idx[-1] < numel and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(idx, bench.dump_sample_index(numel))
+    # three float64 arrays per output: within 64 MB in all
+    assert 3 * 8 * bench.DUMP_MAX_WORDS <= 64 * 10**6
+    # every batch entry and tower of the headline output is sampled
+    assert len(np.unique(idx // 65536)) == 1024 * 16
+
+
 def test_roofline_uses_only_matching_counters(tmp_path, monkeypatch):
     import bench
 
