@@ -2,8 +2,10 @@
 ofhe_hip_bv_core; keyswitch-bv.cpp:302-340, dcrtpoly-impl.h:266-288) through
 the C ABI, bit-exact against oracle/keyswitch.py (pinned by the identities of
 tests/test_bv_oracle.py).  Shapes cover the unfused path (N <= 2^12: lift
-kernel + transform), the fused lift in k_cols (2^13..2^15, 2^17) and in
-k_tcols (2^16); a lower level uses the first towers of longer keys."""
+kernel + transform), the fused lift in k_cols (2^13 and 2^17 here) and in
+k_tcols (2^16); a lower level uses the first towers of longer keys.  2^15,
+the other plan splits and chains of mixed modulus size are in
+tests/test_gpu_mixed_moduli.py."""
 import numpy as np
 import pytest
 

@@ -6,7 +6,11 @@ what they do not: ring dimensions 2^1 .. 2^17, ragged tower and batch counts,
 moduli of 22 to 60 bits that are either near a power of two (the special
 q = 2^L - d form the kernels detect per plan) or drawn anywhere in their
 range (the generic kernels), and inputs whose words are 0, 1 and q - 1 at
-random positions.  Each case is reproducible from its seed.  The oracle
+random positions.  Each case is reproducible from its seed.  192 cases here:
+96 over the plan ops, 48 over the base conversion, 48 over ApproxModUp /
+ApproxModDown.  The ops built on top of these -- the rescaling callers, BV and
+the HYBRID key-switch engine with its options -- are swept the same way in
+tests/test_gpu_fuzz_tier2.py (144 cases drawn by tests/tier2_cases.py).  The oracle
 follows the reference loops (transformnat-impl.h:300-354, 492-552;
 mubintvecnat.cpp:245-367; dcrtpoly-impl.h:1034-1063)."""
 import os

@@ -3,8 +3,12 @@ ofhe_hip_mod_reduce; DCRTPolyImpl::DropLastElementAndScale / ModReduce,
 dcrtpoly-impl.h:746-812) through the C ABI, bit-exact against
 oracle/keyswitch.py (itself checked against exact big-integer semantics in
 tests/test_rescale_oracle.py).  Shapes cover the small-N path (k_small /
-k_sub_scale), the fused forward-subtract block pass (N >= 2^12), N = 2^16's
-k_tcols split and N = 2^17; both forms; in place and with padded strides."""
+k_sub_scale), the fused forward-subtract block pass (N >= 2^12), the
+switch-loading column pass at 2^13 (the lower-level and aliasing tests below),
+2^14 and 2^17, N = 2^16's k_tcols split; both forms; in place and with padded
+strides.  Every modulus here comes from O.moduli_chain (each tower just above
+the dropped one); 2^15, the other plan splits and chains of mixed modulus size
+are in tests/test_gpu_mixed_moduli.py."""
 import numpy as np
 import pytest
 
