@@ -333,6 +333,33 @@ int ofhe_hip_ks_mod_down(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* x, uint
 int ofhe_hip_ks_core(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* c, const uint64_t* key_b,
                      const uint64_t* key_a, uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch,
                      void* stream);
+/* Hoisted rotations: nrot rotations of one digit set, the digits of
+ * ofhe_hip_ks_precompute ([batch][beta][size_ql + size_p][N]) decomposed once.
+ * auto_index[r] (host array) is rotation r's automorphism index, any odd value,
+ * taken mod 2N; key_b[r] / key_a[r] (host arrays of device pointers) are its
+ * evaluation key, laid out as for ofhe_hip_ks_fast_core_ext.  The pointers and
+ * indices travel in kernel arguments: nothing is staged and nothing
+ * synchronises.  Canonical outputs; out0 must differ from out1.
+ *
+ * LeveledSHECKKSRNS::EvalFastRotationExt (ckksrns-leveledshe.cpp:402-457), over Ql|P:
+ *   out0[r][b] = sigma_k(sum_j digits_j * b_j^(r) + c0[b] * (P mod q_i) on the Q towers)
+ *   out1[r][b] = sigma_k(sum_j digits_j * a_j^(r))
+ * c0: [batch][size_ql][N] evaluation form, or NULL for addFirst = false;
+ * out0, out1: [nrot][batch][size_ql + size_p][N]. */
+int ofhe_hip_ks_fast_rotation_ext(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* digits, const uint64_t* c0,
+                                  uint32_t nrot, const uint32_t* auto_index, const uint64_t* const* key_b,
+                                  const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint32_t batch,
+                                  void* stream);
+/* LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:471-513), in the
+ * reference's order (ModDown, += c0, automorphism):
+ *   out0[r][b] = sigma_k(ModDown(sum_j digits_j * b_j^(r)) + c0[b])
+ *   out1[r][b] = sigma_k(ModDown(sum_j digits_j * a_j^(r)))
+ * with t as in ofhe_hip_ks_mod_down; c0 is required;
+ * out0, out1: [nrot][batch][size_ql][N]. */
+int ofhe_hip_ks_fast_rotation(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* digits, const uint64_t* c0,
+                              uint32_t nrot, const uint32_t* auto_index, const uint64_t* const* key_b,
+                              const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint64_t t,
+                              uint32_t batch, void* stream);
 
 /* ---- element maps ---- */
 /* NativeVectorT::SwitchModulus (mubintvecnat.cpp:111-136) on n words:

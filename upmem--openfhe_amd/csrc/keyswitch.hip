@@ -319,6 +319,7 @@ struct KsLevel {
     ofhe_bconv_t down = nullptr;        // P -> Ql
     KsTower* d_tow = nullptr;           // [size_ql + size_p]
     TowerScalar* d_pinv = nullptr;      // [size_ql] P^-1 mod q_i
+    TowerScalar* d_pmodq = nullptr;     // [size_ql] P mod q_i (m_PModq, rns-cryptoparameters.h:340)
     std::map<u64, TowerScalar*> tscale; // t -> [size_p] t^-1 mod p_j, then [size_ql] t mod q_i
 };
 
@@ -341,6 +342,7 @@ static void level_free(KsLevel* L) {
     if (L->down) ofhe_hip_bconv_destroy(L->down);
     (void)hipFree(L->d_tow);
     (void)hipFree(L->d_pinv);
+    (void)hipFree(L->d_pmodq);
     for (auto& kv : L->tscale) (void)hipFree(kv.second);
     delete L;
 }
@@ -489,15 +491,21 @@ static int level_get(ofhe_ks_t k, u32 size_ql, KsLevel** out) {
             limb_red_consts(m, lr);
             tow[i] = KsTower{m, (u64)mu, (u64)(mu >> 64), (isq ? i : k->size_q + i - l) * N, lr[0], lr[1], lr[2]};
         }
-        std::vector<TowerScalar> pinv(l);
-        for (u32 i = 0; i < l; i++)
-            pinv[i] = scalar_of(k->q[i], invmod(prod_mod(k->p.data(), P, P, k->q[i]), k->q[i]));
+        std::vector<TowerScalar> pinv(l), pmodq(l);
+        for (u32 i = 0; i < l; i++) {
+            const u64 pm = prod_mod(k->p.data(), P, P, k->q[i]);
+            pinv[i] = scalar_of(k->q[i], invmod(pm, k->q[i]));
+            pmodq[i] = scalar_of(k->q[i], pm);
+        }
         hipError_t e = hipSetDevice(k->ctx->device);
         if (e == hipSuccess) e = hipMalloc(&L->d_tow, sizeof(KsTower) * tow.size());
         if (e == hipSuccess) e = hipMalloc(&L->d_pinv, sizeof(TowerScalar) * pinv.size());
+        if (e == hipSuccess) e = hipMalloc(&L->d_pmodq, sizeof(TowerScalar) * pmodq.size());
         if (e == hipSuccess) e = upload_blocking(L->d_tow, tow.data(), sizeof(KsTower) * tow.size());
         if (e == hipSuccess)
             e = upload_blocking(L->d_pinv, pinv.data(), sizeof(TowerScalar) * pinv.size());
+        if (e == hipSuccess)
+            e = upload_blocking(L->d_pmodq, pmodq.data(), sizeof(TowerScalar) * pmodq.size());
         if (e != hipSuccess) rc = fail(OFHE_ERR_HIP, std::string("level upload: ") + hipGetErrorString(e));
     }
     if (rc != OFHE_OK) {
@@ -743,6 +751,121 @@ int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uin
     RCCHK(ks_mod_down_impl(k, L, c0, out0, t, batch, fk.f[0]));
     RCCHK(ks_mod_down_impl(k, L, c1, out1, t, batch, fk.f[1]));
     return fk.join();
+}
+
+// ---------------------------------------------------------------------------
+// Hoisted rotations: many keys over one digit set
+// ---------------------------------------------------------------------------
+// inverse of an odd k modulo 2^32 (Newton: k is its own inverse mod 8)
+static u32 inv_odd32(u32 k) {
+    u32 x = k;
+    for (int i = 0; i < 4; i++) x *= 2 - k * x;
+    return x;
+}
+
+// Argument checks shared by the two calls; kinv[r] = auto_index[r]^-1.
+static int rot_check(ofhe_ks_t k, u32 size_ql, const u64* digits, u32 nrot, const u32* auto_index,
+                     const u64* const* key_b, const u64* const* key_a, const u64* out0, const u64* out1, u32 batch,
+                     std::vector<u32>& kinv) {
+    RCCHK(ks_check(k, size_ql, batch));
+    if (!digits || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (!auto_index || !key_b || !key_a) return fail(OFHE_ERR_ARG, "NULL index or key pointer array");
+    if (nrot == 0) return fail(OFHE_ERR_ARG, "nrot must be >= 1");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    kinv.resize(nrot);
+    for (u32 r = 0; r < nrot; r++) {
+        if (!key_b[r] || !key_a[r]) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
+        if (auto_index[r] % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
+        kinv[r] = inv_odd32(auto_index[r]);
+    }
+    return OFHE_OK;
+}
+
+// k_ks_inner_rot / k_ks_inner_rot_wide for nrot <= KS_ROT_CAP rotations
+static int ks_inner_rot(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* digits, const u64* c0, u32 nrot,
+                        const u32* kinv, const u64* const* key_b, const u64* const* key_a, u64* out0, u64* out1,
+                        u64 rot_stride, u32 batch, hipStream_t s) {
+    KsRot R{};
+    for (u32 r = 0; r < nrot; r++) {
+        R.kb[r] = key_b[r];
+        R.ka[r] = key_a[r];
+        R.kinv[r] = kinv[r];
+    }
+    const u32 towers = size_ql + k->size_p;
+    const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
+    const u64 nthreads = (u64)batch * towers << k->log_n;
+    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
+#define OFHE_KS_ROT(B_)                                                                                        \
+    hipLaunchKernelGGL((k_ks_inner_rot<B_>), g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R, nrot, out0, out1, \
+                       key_stride, rot_stride, nthreads, k->log_n, towers, size_ql)
+    switch (L->beta) {
+        case 1: OFHE_KS_ROT(1); break;
+        case 2: OFHE_KS_ROT(2); break;
+        case 3: OFHE_KS_ROT(3); break;
+        case 4: OFHE_KS_ROT(4); break;
+        default:
+            hipLaunchKernelGGL(k_ks_inner_rot_wide, g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R, nrot, out0,
+                               out1, key_stride, rot_stride, nthreads, L->beta, k->log_n, towers, size_ql);
+    }
+#undef OFHE_KS_ROT
+    return post_launch();
+}
+
+int ofhe_hip_ks_fast_rotation_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t* digits, const uint64_t* c0,
+                                  uint32_t nrot, const uint32_t* auto_index, const uint64_t* const* key_b,
+                                  const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint32_t batch,
+                                  void* stream) {
+    std::vector<u32> kinv;
+    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv));
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    const u64 rot_stride = (u64)batch * (size_ql + k->size_p) << k->log_n;
+    for (u32 r0 = 0; r0 < nrot; r0 += KS_ROT_CAP)
+        RCCHK(ks_inner_rot(k, L, size_ql, digits, c0, std::min(KS_ROT_CAP, nrot - r0), kinv.data() + r0, key_b + r0,
+                           key_a + r0, out0 + r0 * rot_stride, out1 + r0 * rot_stride, rot_stride, batch,
+                           pick(stream)));
+    return OFHE_OK;
+}
+
+int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* digits, const uint64_t* c0,
+                              uint32_t nrot, const uint32_t* auto_index, const uint64_t* const* key_b,
+                              const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint64_t t,
+                              uint32_t batch, void* stream) {
+    std::vector<u32> kinv;
+    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv));
+    if (!c0) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    hipStream_t s = pick(stream);
+    const TowerScalar* tt = nullptr;
+    if (t) RCCHK(level_t_tables(k, L, t, &tt));
+    const u32 l = L->size_ql, P = k->size_p;
+    const u64 N = 1ull << k->log_n, poly = (u64)(l + P) * N, per_rot = (u64)batch * l * N;
+    ModDownArgs A{k->plan, k->plan, 0, k->size_q, l, P, L->down->args, L->d_pinv,
+                  tt ? tt : nullptr, tt ? tt + P : nullptr, k->bcols, k->icol};
+    u32 one[KS_ROT_CAP];
+    for (auto& v : one) v = 1;
+    // the order of the reference: ModDown, += c0, then the automorphism
+    // (ModDown and the automorphism do not commute bit for bit)
+    for (u32 r0 = 0; r0 < nrot; r0 += KS_ROT_CAP) {
+        const u32 nr = std::min(KS_ROT_CAP, nrot - r0);
+        Scratch ct, md;
+        RCCHK(ct.alloc((size_t)2 * nr * batch * poly * 8, s, k->ctx));
+        RCCHK(md.alloc((size_t)2 * nr * per_rot * 8, s, k->ctx));
+        // ct0 of every (rotation, batch entry), then ct1 of every one: the two
+        // ModDowns of all rotations run as one launch set over nr * batch
+        u64* ct1 = ct.w() + (u64)nr * batch * poly;
+        u64* md1 = md.w() + (u64)nr * per_rot;
+        RCCHK(ks_inner_rot(k, L, size_ql, digits, nullptr, nr, one, key_b + r0, key_a + r0, ct.w(), ct1,
+                           (u64)batch * poly, batch, s));
+        RCCHK(mod_down_run2(A, ct.w(), poly, md.w(), md1, (u64)l * N, nr * batch, s));
+        KsRotIdx I{};
+        for (u32 r = 0; r < nr; r++) I.kinv[r] = kinv[r0 + r];
+        hipLaunchKernelGGL(k_add_automorphism, dim3(grid_for(per_rot), nr), dim3(256), 0, s, L->d_tow, md.w(), md1,
+                           c0, out0 + r0 * per_rot, out1 + r0 * per_rot, I, per_rot, k->log_n, l);
+        RCCHK(post_launch());
+    }
+    return OFHE_OK;
 }
 
 // ---------------------------------------------------------------------------

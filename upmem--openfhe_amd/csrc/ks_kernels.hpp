@@ -236,6 +236,175 @@ __global__ __launch_bounds__(256) void k_ks_inner_bs(const KsTower* __restrict__
     }
 }
 
+// Hoisted rotations: LeveledSHECKKSRNS::EvalFastRotationExt
+// (ckksrns-leveledshe.cpp:402-457) and the inner product of
+// LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:471-513) for up to
+// KS_ROT_CAP rotations of one digit set per launch.  The per-rotation key
+// pointers and automorphism indices travel in the kernel arguments (nothing
+// is staged); kinv[r] is the inverse of rotation r's index k modulo 2^32,
+// hence modulo 2N.
+constexpr u32 KS_ROT_CAP = 16;
+struct KsRot {
+    const u64* kb[KS_ROT_CAP];
+    const u64* ka[KS_ROT_CAP];
+    u32 kinv[KS_ROT_CAP];
+};
+struct KsRotIdx {
+    u32 kinv[KS_ROT_CAP];
+};
+
+// AutomorphismTransform(k) in evaluation form (poly-impl.h:338-364) sets
+// dst[rev(j)] = src[rev(j')] with 2 j' + 1 = k (2 j + 1) mod 2N.  A thread
+// that holds the value of storage position s = rev(j') therefore writes it to
+// rev(j) with 2 j + 1 = k^-1 (2 j' + 1) mod 2N (the product wraps mod 2^32,
+// which 2N divides).  Aligned blocks of 2^m storage words map onto aligned
+// blocks of 2^m words, so a wave's 64 stores fill whole 128-byte lines.
+__device__ __forceinline__ u32 rot_dest(u32 s, u32 kinv, u32 log_n) {
+    const u32 j = __builtin_bitreverse32(s) >> (32 - log_n);
+    const u32 jk = kinv * (2 * j + 1);
+    return __builtin_bitreverse32((jk >> 1) & ((1u << log_n) - 1)) >> (32 - log_n);
+}
+
+// Digit-stationary inner product: a thread owns one (batch entry, tower,
+// storage position), loads and limb-splits its BETA digit words once and
+// walks the rotations of the launch: per rotation it loads the 2 BETA key
+// words (the next rotation's before the current one is reduced), accumulates
+// the 30-bit limb sums of k_ks_inner_bs, reduces, adds c0 * (P mod q_t) on
+// the Q towers when c0 is given (addFirst) and stores at the position the
+// rotation's automorphism sends its word to.  Outputs: [nrot][batch][towers][N]
+// with rot_stride words between rotations.  With kinv = 1 it is the plain
+// multi-key inner product of the non-Ext path.  (An exchange of the
+// workgroup's results through LDS, so that the stores leave in position
+// order, measured the same as this scatter: DESIGN.md "Hoisted rotations".)
+template <int BETA>
+__global__ __launch_bounds__(256) void k_ks_inner_rot(const KsTower* __restrict__ tw, const u64* __restrict__ digits,
+                                                      const u64* __restrict__ c0,
+                                                      const TowerScalar* __restrict__ pmodq, KsRot rot, u32 nrot,
+                                                      u64* __restrict__ out0, u64* __restrict__ out1, u64 key_stride,
+                                                      u64 rot_stride, u64 nthreads, u32 log_n, u32 towers,
+                                                      u32 size_ql) {
+    OFHE_VGPR_FLOOR();
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nthreads) return;
+    const u32 row = (u32)(i >> log_n), s = (u32)(i & ((1ull << log_n) - 1));
+    const u32 b = row / towers, t = row % towers;
+    const KsTower T = tw[t];
+    const LimbRed R{T.m, T.r60, T.r60p, T.mu1};
+    const u64 poly = (u64)towers << log_n;
+    const u64 inner = (u64)t << log_n;
+    u32 x0[BETA], x1[BETA];
+#pragma unroll
+    for (int j = 0; j < BETA; j++) {
+        const u64 v = ld_s(digits + ((u64)b * BETA + j) * poly + inner + s);
+        x0[j] = (u32)(v & LIMB_MASK);
+        x1[j] = (u32)(v >> LIMB);
+    }
+    u64 add = 0;  // c0 * PModq on the Q towers (ckksrns-leveledshe.cpp:436-445)
+    if (c0 && t < size_ql) {
+        const TowerScalar ps = pmodq[t];
+        add = shoup_canon(ld_s(c0 + (((u64)b * size_ql + t) << log_n) + s), ps.s, ps.sp, ps.q);
+    }
+    const u64 koff = T.key_off + s;
+    u64 nb[BETA], na[BETA];
+    auto load = [&](u32 r) {
+        const u64* pb = rot.kb[r] + koff;
+        const u64* pa = rot.ka[r] + koff;
+#pragma unroll
+        for (int j = 0; j < BETA; j++) {
+            nb[j] = ld_s(pb + (u64)j * key_stride);
+            na[j] = ld_s(pa + (u64)j * key_stride);
+        }
+    };
+    load(0);
+    for (u32 r = 0; r < nrot; r++) {
+        u64 acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+        for (int j = 0; j < BETA; j++) {
+            const u64 w[2] = {nb[j], na[j]};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const u32 w0 = (u32)(w[k] & LIMB_MASK), w1 = (u32)(w[k] >> LIMB);
+                acc[k][0] = mad32(x0[j], w0, acc[k][0]);
+                acc[k][1] = mad32(x0[j], w1, acc[k][1]);
+                acc[k][2] = mad32(x1[j], w0, acc[k][2]);
+                acc[k][3] = mad32(x1[j], w1, acc[k][3]);
+            }
+        }
+        if (r + 1 < nrot) load(r + 1);
+        const u64 r0 = csub(limb_reduce<false>(acc[0][0], acc[0][1], acc[0][2], acc[0][3], R) + add, T.m);
+        const u64 r1 = limb_reduce<false>(acc[1][0], acc[1][1], acc[1][2], acc[1][3], R);
+        const u64 o = (u64)r * rot_stride + (u64)b * poly + inner + rot_dest(s, rot.kinv[r], log_n);
+        st_s(out0 + o, r0);
+        st_s(out1 + o, r1);
+    }
+}
+
+// The same for beta > 4: a runtime digit count, the digits re-read per
+// rotation, exact 128-bit sums and barrett128 as in k_ks_inner.
+__global__ __launch_bounds__(256) void k_ks_inner_rot_wide(const KsTower* __restrict__ tw,
+                                                           const u64* __restrict__ digits,
+                                                           const u64* __restrict__ c0,
+                                                           const TowerScalar* __restrict__ pmodq, KsRot rot, u32 nrot,
+                                                           u64* __restrict__ out0, u64* __restrict__ out1,
+                                                           u64 key_stride, u64 rot_stride, u64 nthreads, u32 beta,
+                                                           u32 log_n, u32 towers, u32 size_ql) {
+    OFHE_VGPR_FLOOR();
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nthreads) return;
+    const u32 row = (u32)(i >> log_n), s = (u32)(i & ((1ull << log_n) - 1));
+    const u32 b = row / towers, t = row % towers;
+    const KsTower T = tw[t];
+    const u64 poly = (u64)towers << log_n;
+    const u64 inner = (u64)t << log_n;
+    const u64* d = digits + (u64)b * beta * poly + inner + s;
+    u64 add = 0;
+    if (c0 && t < size_ql) {
+        const TowerScalar ps = pmodq[t];
+        add = shoup_canon(ld_s(c0 + (((u64)b * size_ql + t) << log_n) + s), ps.s, ps.sp, ps.q);
+    }
+    const u64 koff = T.key_off + s;
+    for (u32 r = 0; r < nrot; r++) {
+        const u64* pb = rot.kb[r] + koff;
+        const u64* pa = rot.ka[r] + koff;
+        u64 bl = 0, bh = 0, al = 0, ah = 0;
+        for (u32 j = 0; j < beta; j++) {
+            const u64 x = d[(u64)j * poly];
+            u64 l, h;
+            mul128(x, ld_s(pb + (u64)j * key_stride), l, h);
+            bl += l;
+            bh += h + (bl < l);
+            mul128(x, ld_s(pa + (u64)j * key_stride), l, h);
+            al += l;
+            ah += h + (al < l);
+        }
+        const u64 o = (u64)r * rot_stride + (u64)b * poly + inner + rot_dest(s, rot.kinv[r], log_n);
+        st_s(out0 + o, csub(barrett128(bl, bh, T.m, T.mu_lo, T.mu_hi) + add, T.m));
+        st_s(out1 + o, barrett128(al, ah, T.m, T.mu_lo, T.mu_hi));
+    }
+}
+
+// Tail of EvalFastRotation (base-leveledshe.cpp:500-505) for the rotations of
+// one launch (blockIdx.y): out0 = sigma_k(md0 + c0), out1 = sigma_k(md1) over
+// [nrot][batch][towers][N]; md0, md1 are the two ModDown results, c0:
+// [batch][towers][N], shared by the rotations.
+__global__ __launch_bounds__(256) void k_add_automorphism(const KsTower* __restrict__ tw,
+                                                          const u64* __restrict__ md0, const u64* __restrict__ md1,
+                                                          const u64* __restrict__ c0, u64* __restrict__ out0,
+                                                          u64* __restrict__ out1, KsRotIdx rot, u64 per_rot,
+                                                          u32 log_n, u32 towers) {
+    OFHE_VGPR_FLOOR();
+    const u64 step = (u64)gridDim.x * blockDim.x;
+    const u32 kinv = rot.kinv[blockIdx.y];
+    const u64 base = (u64)blockIdx.y * per_rot;
+    for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < per_rot; e += step) {
+        const u32 row = (u32)(e >> log_n), s = (u32)(e & ((1ull << log_n) - 1));
+        const u64 m = tw[row % towers].m;
+        const u64 o = base + ((u64)row << log_n) + rot_dest(s, kinv, log_n);
+        st_s(out0 + o, csub(ld_s(md0 + base + e) + ld_s(c0 + e), m));
+        st_s(out1 + o, ld_s(md1 + base + e));
+    }
+}
+
 // NativeVectorT::SwitchModulus (mubintvecnat.cpp:111-136), value for value.
 __global__ __launch_bounds__(256) void k_switch_modulus(const u64* src, u64* dst, u64 n, u64 om, u64 nm) {
     OFHE_VGPR_FLOOR();

@@ -855,9 +855,111 @@ public:
         return {std::move(o0), std::move(o1)};
     }
 
+    // The digits of one ciphertext's c1 (EvalKeySwitchPrecomputeCore), kept on
+    // the device for any number of hoisted rotations.
+    struct HoistedDigits {
+        DeviceBuffer buf;        // [batch][beta][size_ql + sizeP][N]
+        uint32_t size_ql = 0, batch = 0;
+    };
+    // one evaluation key per rotation: the b and a polynomials, as KeySwitchCore takes them
+    typedef std::pair<const DCRTPolyHip*, const DCRTPolyHip*> RotationKey;
+    typedef std::vector<std::pair<DCRTPolyHip, DCRTPolyHip>> Rotations;
+
+    // LeveledSHEBase::EvalFastRotationPrecompute (base-leveledshe.cpp:462-469)
+    HoistedDigits FastRotationPrecompute(const DCRTPolyHip& c1) const {
+        if (c1.GetFormat() != Format::EVALUATION)
+            throw math_error("FastRotationPrecompute: EVALUATION form expected");
+        const uint32_t l = (uint32_t)c1.GetParams()->Towers();
+        if (l > sizeQ_) throw math_error("FastRotationPrecompute: ciphertext has more towers than Q");
+        uint32_t beta = 0;
+        check(ofhe_hip_ks_digits(h_, l, nullptr, &beta), "FastRotationPrecompute");
+        HoistedDigits d;
+        d.buf = DeviceBuffer(c1.GetParams()->manager(),
+                             (size_t)c1.Batch() * beta * (l + sizeP_) * c1.GetParams()->GetRingDimension());
+        d.size_ql = l;
+        d.batch = c1.Batch();
+        check(ofhe_hip_ks_precompute(h_, l, c1.data(), d.buf.get(), d.batch, nullptr), "FastRotationPrecompute");
+        return d;
+    }
+
+    // LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:471-513) for every
+    // index of autoIndex: one (c0', c1') pair per rotation over c0's params.
+    Rotations FastRotation(const DCRTPolyHip& c0, const HoistedDigits& digits, const std::vector<uint32_t>& autoIndex,
+                           const std::vector<RotationKey>& keys, uint64_t t = 0) const {
+        rot_check("FastRotation", &c0, digits, autoIndex, keys);
+        if (c0.GetParams()->Towers() != digits.size_ql)
+            throw math_error("FastRotation: c0 and the digits are at different levels");
+        return rot_run(c0.GetParams(), digits, autoIndex, keys, [&](const KeyPtrs& k, uint64_t* o0, uint64_t* o1) {
+            check(ofhe_hip_ks_fast_rotation(h_, digits.size_ql, digits.buf.get(), c0.data(),
+                                            (uint32_t)autoIndex.size(), autoIndex.data(), k.b.data(), k.a.data(), o0,
+                                            o1, t, digits.batch, nullptr),
+                  "FastRotation");
+        });
+    }
+
+    // LeveledSHECKKSRNS::EvalFastRotationExt (ckksrns-leveledshe.cpp:402-457):
+    // pairs over the caller's Ql|P params; c0 = nullptr for addFirst = false.
+    Rotations FastRotationExt(const DCRTPolyHip* c0, const HoistedDigits& digits,
+                              const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys,
+                              const std::shared_ptr<DCRTParams>& paramsQlP) const {
+        rot_check("FastRotationExt", c0, digits, autoIndex, keys);
+        if (c0 && c0->GetParams()->Towers() != digits.size_ql)
+            throw math_error("FastRotationExt: c0 and the digits are at different levels");
+        if (!paramsQlP || paramsQlP->Towers() != digits.size_ql + sizeP_)
+            throw math_error("FastRotationExt: paramsQlP must have the level's towers plus P");
+        return rot_run(paramsQlP, digits, autoIndex, keys, [&](const KeyPtrs& k, uint64_t* o0, uint64_t* o1) {
+            check(ofhe_hip_ks_fast_rotation_ext(h_, digits.size_ql, digits.buf.get(), c0 ? c0->data() : nullptr,
+                                                (uint32_t)autoIndex.size(), autoIndex.data(), k.b.data(),
+                                                k.a.data(), o0, o1, digits.batch, nullptr),
+                  "FastRotationExt");
+        });
+    }
+
     ofhe_ks_t handle() const { return h_; }
 
 private:
+    struct KeyPtrs {
+        std::vector<const uint64_t*> b, a;
+    };
+    void rot_check(const char* op, const DCRTPolyHip* c0, const HoistedDigits& digits,
+                   const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys) const {
+        const std::string w(op);
+        if (!digits.buf.get() || !digits.size_ql) throw math_error(w + ": empty digits");
+        if (c0 && c0->GetFormat() != Format::EVALUATION) throw math_error(w + ": EVALUATION form expected");
+        if (c0 && c0->Batch() != digits.batch) throw math_error(w + ": batch mismatch");
+        if (autoIndex.empty() || autoIndex.size() != keys.size())
+            throw math_error(w + ": one evaluation key per automorphism index required");
+        for (const auto& k : keys)
+            if (!k.first || !k.second || k.first->Batch() != numPartQ_ || k.second->Batch() != numPartQ_ ||
+                k.first->GetParams()->Towers() != sizeQ_ + sizeP_ || k.second->GetParams()->Towers() != sizeQ_ + sizeP_)
+                throw math_error(w + ": evaluation key must be numPartQ polynomials over Q|P");
+    }
+    // The C ABI writes [nrot][batch][towers][N]; every rotation gets a
+    // DCRTPolyHip of its own, filled by one device copy.
+    template <class F>
+    Rotations rot_run(const std::shared_ptr<DCRTParams>& op, const HoistedDigits& digits,
+                      const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys, F call) const {
+        KeyPtrs k;
+        for (const auto& key : keys) {
+            k.b.push_back(key.first->data());
+            k.a.push_back(key.second->data());
+        }
+        const size_t per = (size_t)digits.batch * op->Towers() * op->GetRingDimension(), nrot = autoIndex.size();
+        DeviceBuffer all0(op->manager(), nrot * per), all1(op->manager(), nrot * per);
+        call(k, all0.get(), all1.get());
+        Rotations out;
+        for (size_t r = 0; r < nrot; r++) {
+            DCRTPolyHip o0(op, Format::EVALUATION, digits.batch, DCRTPolyHip::Uninit{}),
+                o1(op, Format::EVALUATION, digits.batch, DCRTPolyHip::Uninit{});
+            check(ofhe_hip_copy_device(op->manager()->ctx(), o0.data(), all0.get() + r * per, per * 8, nullptr),
+                  "FastRotation");
+            check(ofhe_hip_copy_device(op->manager()->ctx(), o1.data(), all1.get() + r * per, per * 8, nullptr),
+                  "FastRotation");
+            out.emplace_back(std::move(o0), std::move(o1));
+        }
+        return out;
+    }
+
     ofhe_ks_t h_ = nullptr;
     size_t sizeQ_ = 0, sizeP_ = 0;
     uint32_t numPartQ_ = 0;

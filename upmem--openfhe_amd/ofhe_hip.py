@@ -12,7 +12,10 @@ Host-side mirror of the reference's offload interface for the hot path:
 * ``approx_mod_up`` / ``approx_mod_down`` ~ ``DCRTPolyImpl::ApproxModUp`` /
   ``ApproxModDown`` (dcrtpoly-impl.h:1085-1175).
 * ``KeySwitch`` ~ ``KeySwitchHYBRID`` (pke/lib/keyswitch/keyswitch-hybrid.cpp:325-482)
-  with the tables of ``CryptoParametersRNS::PrecomputeCRTTables``.
+  with the tables of ``CryptoParametersRNS::PrecomputeCRTTables``; its
+  ``fast_rotation`` / ``fast_rotation_ext`` ~ ``EvalFastRotation``
+  (base-leveledshe.cpp:471-513) / ``EvalFastRotationExt``
+  (ckksrns-leveledshe.cpp:402-457) for many keys over one digit set.
 * ``switch_modulus`` / ``NTTPlan.automorphism`` ~ ``NativeVectorT::SwitchModulus``
   (mubintvecnat.cpp:111-136) / ``PolyImpl::AutomorphismTransform`` (poly-impl.h:312-365).
 
@@ -112,6 +115,13 @@ _SIGS = {
                                             _vp]),
     "ofhe_hip_ks_core": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
                                         ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_fast_rotation_ext": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_vp),
+                                                     ctypes.POINTER(_vp), _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_fast_rotation": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_vp),
+                                                 ctypes.POINTER(_vp), _vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                 _vp]),
     "ofhe_hip_switch_modulus": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                _vp]),
     "ofhe_hip_automorphism": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
@@ -130,6 +140,7 @@ _SIGS = {
 }
 
 COMM_ID_BYTES = 128  # OFHE_COMM_ID_BYTES
+KS_ROT_CAP = 16  # rotations per launch of the hoisted-rotation calls (csrc/ks_kernels.hpp); more run in chunks
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -539,6 +550,42 @@ class KeySwitch:
              batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_ks_core(self._h, int(size_ql), _vp(c), _vp(key_b), _vp(key_a), _vp(out0),
                                       _vp(out1), int(t), int(batch), _vp(stream or None)))
+
+    @staticmethod
+    def _rot_args(auto_indices, key_b_ptrs, key_a_ptrs):
+        """(nrot, index array, key pointer arrays) of the hoisted-rotation calls; None stays NULL."""
+        def ptrs(v):
+            return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
+
+        for v in (key_b_ptrs, key_a_ptrs):
+            if auto_indices is not None and v is not None and len(v) != len(auto_indices):
+                raise MathError("one evaluation key per automorphism index required")
+        if auto_indices is None:
+            return 0, None, ptrs(key_b_ptrs), ptrs(key_a_ptrs)
+        for k in auto_indices:
+            if not 0 <= int(k) < 1 << 32:
+                raise MathError("automorphism index must fit 32 bits")
+        idx = (ctypes.c_uint32 * len(auto_indices))(*[int(k) for k in auto_indices])
+        return len(auto_indices), idx, ptrs(key_b_ptrs), ptrs(key_a_ptrs)
+
+    def fast_rotation_ext(self, size_ql: int, digits: int, c0: int, auto_indices: Sequence[int],
+                          key_b_ptrs: Sequence[int], key_a_ptrs: Sequence[int], out0: int, out1: int,
+                          batch: int = 1, stream: int = 0) -> None:
+        """LeveledSHECKKSRNS::EvalFastRotationExt (ckksrns-leveledshe.cpp:402-457) for every index of
+        auto_indices over one digit set (precompute's output); c0 = 0: addFirst = false.
+        out0, out1: [nrot][batch][size_ql + size_p][N]."""
+        n, idx, kb, ka = self._rot_args(auto_indices, key_b_ptrs, key_a_ptrs)
+        _check(lib().ofhe_hip_ks_fast_rotation_ext(self._h, int(size_ql), _vp(digits), _vp(c0 or None), n, idx, kb,
+                                                   ka, _vp(out0), _vp(out1), int(batch), _vp(stream or None)))
+
+    def fast_rotation(self, size_ql: int, digits: int, c0: int, auto_indices: Sequence[int],
+                      key_b_ptrs: Sequence[int], key_a_ptrs: Sequence[int], out0: int, out1: int, t: int = 0,
+                      batch: int = 1, stream: int = 0) -> None:
+        """LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:471-513) for every index of auto_indices
+        over one digit set.  out0, out1: [nrot][batch][size_ql][N]."""
+        n, idx, kb, ka = self._rot_args(auto_indices, key_b_ptrs, key_a_ptrs)
+        _check(lib().ofhe_hip_ks_fast_rotation(self._h, int(size_ql), _vp(digits), _vp(c0 or None), n, idx, kb, ka,
+                                               _vp(out0), _vp(out1), int(t), int(batch), _vp(stream or None)))
 
 
 def comm_unique_id() -> bytes:
