@@ -15,7 +15,10 @@
  *   - the HYBRID key-switching core built on them
  *       (src/pke/lib/keyswitch/keyswitch-hybrid.cpp:325-482),
  *   - NativeVectorT::SwitchModulus and PolyImpl::AutomorphismTransform
- *       (mubintvecnat.cpp:111-136, poly-impl.h:312-365).
+ *       (mubintvecnat.cpp:111-136, poly-impl.h:312-365),
+ *   - the BFV (HPS) multiplication's SwitchCRTBasis / ExpandCRTBasis /
+ *     FastExpandCRTBasisPloverQ / ScaleAndRound
+ *       (dcrtpoly-impl.h:1178-1230, 1311-1358, 1413-1466, 1876-1955).
  *
  * Conventions
  *   - Plain C, no exceptions cross the ABI. Every entry point returns an int
@@ -415,6 +418,101 @@ int ofhe_hip_bv_precompute(ofhe_plan_t plan, uint32_t towers, const uint64_t* c,
 int ofhe_hip_bv_core(ofhe_plan_t plan, uint32_t towers, const uint64_t* digits, const uint64_t* key_b,
                      const uint64_t* key_a, uint32_t key_towers, uint64_t* out0, uint64_t* out1, uint32_t batch,
                      void* stream);
+
+/* ---- BFV multiplication, HPS family: what LeveledSHEBFVRNS::EvalMult
+ *      (pke/lib/scheme/bfvrns/bfvrns-leveledshe.cpp:168-408) runs between the
+ *      tensor product and key switching.  All results are bit-exact with the
+ *      reference's HAVE_INT128 && NATIVEINT == 64 branches, the value of the
+ *      floating-point correction term included.
+ *
+ *      Floating-point contract.  nu starts at 0.5.  For source towers
+ *      i = 0, 1, ... in that order: nu = nu + (double(y_i) * qInv[i]) in
+ *      SwitchCRTBasis and nu = nu + (frac[i] * double(x_i)) in ScaleAndRound.
+ *      Every multiply and every add is rounded separately to IEEE double,
+ *      round-to-nearest-even (the reference's baseline x86-64 build): no fused
+ *      multiply-add, no tree or cross-lane reordering of the sum, no float.
+ *      double(uint64) is the correctly rounded conversion (values reach 2^60).
+ *      alpha = floor(nu), and nu >= 0.5 always.  Where a kernel spreads the
+ *      source towers over lanes, only the products are computed apart; the
+ *      additions happen in tower order. ---- */
+
+/* DCRTPolyImpl::SwitchCRTBasis (dcrtpoly-impl.h:1178-1230), the exact switch:
+ * y_i = [x_i QHat_i^-1]_{q_i} canonical, alpha = floor(0.5 + sum_i double(y_i) qInv[i]),
+ * out_j = (sum_i y_i QHatModp_ij mod p_j).ModSubFast(alphaQModp[alpha][j]).
+ * bconv must hold the true CRT tables (QHat^-1 mod q, QHat mod p); layout as
+ * ofhe_hip_approx_switch_crt_basis (x: [batch][size_q][N] -> out:
+ * [batch][size_p][N], coefficient form).  alphaQModp[a][j] = a Q mod p_j,
+ * a = 0 .. size_q (bfvrns-cryptoparameters.cpp:343-350, 418-424) and
+ * qInv[i] = 1.0 / double(q_i) (:270-273, 441-444) are derived from the
+ * handle's moduli on its first exact call (that one call uploads them and waits
+ * on the null stream, as a cache miss of ofhe_hip_approx_mod_down does, so it
+ * cannot run inside a stream capture) and cached; no later call synchronises.
+ * One fused kernel launch; OFHE_BCONV_KERNEL_LIMB / _WIDE on
+ * the handle select the VALU variants here too. */
+int ofhe_hip_switch_crt_basis(ofhe_bconv_t bconv, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+
+/* DCRTPolyImpl::ExpandCRTBasis with resultFormat = EVALUATION
+ * (dcrtpoly-impl.h:1311-1358); signature and layout of ofhe_hip_approx_mod_up:
+ * x [batch][Q][N] (evaluation form when eval_form != 0, else coefficient
+ * form) -> out [batch][Q+P][N], evaluation form.  In the reference's order:
+ * INTT of an evaluation-form input, exact switch Q -> P, NTT of the P towers;
+ * the Q towers of out are the caller's evaluation-form words copied, or the
+ * NTT of a coefficient-form input.  out must not overlap x (OFHE_ERR_ARG), and
+ * the three objects must belong to one context. */
+int ofhe_hip_expand_crt_basis(ofhe_plan_t plan_q, ofhe_plan_t plan_p, ofhe_bconv_t q_to_p, int eval_form,
+                              const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+
+/* DCRTPolyImpl::ScaleAndRound, DCRTPoly -> DCRTPoly (dcrtpoly-impl.h:1876-1955).
+ * x: [batch][size_q + size_p][N], Q towers first, coefficient form.
+ * out_is_q = 0 (HPS): the Q towers are summed, out is [batch][size_p][N] over
+ * P and the "own tower" term uses x[size_q + j]; out_is_q = 1 (HPSPOVERQ): the
+ * P towers are summed, out is [batch][size_q][N] over Q, own tower x[j].
+ * With size_i summed towers and size_o outputs, int_table is host
+ * [size_o][size_i + 1] (tOSHatInvModsDivsModo) and frac host [size_i] doubles
+ * in [0, 1) (tOSHatInvModsDivsFrac), as the pke layer builds them
+ * (bfvrns-cryptoparameters.cpp:289-311, 532-556); Barrett constants are derived
+ * here.  size_i <= 255 (size_i + 1 products must fit the 128-bit sum, the limit
+ * of the reference's DoubleNativeInt) and the output moduli must be odd.  One fused kernel: nu, alpha, the 128-bit sums of size_i + 1 products,
+ * BarrettUint128ModUint64 and + (alpha mod o_j).  Both reference branches
+ * compute floor(nu) mod o_j; floor(nu) is taken exactly as a 128-bit integer
+ * from the double, so nu >= 2^64 is right, and nu == 2^64 (where the
+ * reference's cast is undefined) is defined as floor(nu) mod o_j. */
+typedef struct ofhe_scale_round_s* ofhe_scale_round_t;
+int ofhe_hip_scale_round_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, uint32_t size_p, const uint64_t* q,
+                                const uint64_t* p, int out_is_q, const uint64_t* int_table, const double* frac,
+                                ofhe_scale_round_t* handle);
+int ofhe_hip_scale_round_destroy(ofhe_scale_round_t handle);
+int ofhe_hip_scale_and_round(ofhe_scale_round_t handle, const uint64_t* x, uint64_t* out, uint32_t batch,
+                             void* stream);
+
+/* LeveledSHEBFVRNS::EvalMult for two 2-element ciphertexts
+ * (bfvrns-leveledshe.cpp:168-408), composed from handles the caller created and
+ * keeps alive: plan_q / plan_r / plan_qr (Q towers then R towers), q_to_r and
+ * r_to_q with the true CRT tables, scale_round, and for HPSPOVERQ q_to_r_neg, a
+ * converter created with mNegRlQHatInvModq / qInvModr
+ * (bfvrns-cryptoparameters.cpp:501-523); q_to_r_neg is NULL for HPS.  Every
+ * handle must belong to ctx.
+ * c0, c1, d0, d1: [batch][Q][N] evaluation form; out0..out2: [batch][Q][N] in
+ * coefficient form, as the reference leaves cvMult.
+ *   OFHE_BFV_HPS: ExpandCRTBasis of the four inputs, the tensor product over
+ *     Q|R, INTT, ScaleAndRound to R (out_is_q = 0), exact switch R -> Q.
+ *   OFHE_BFV_HPSPOVERQ (size_r == size_q): ExpandCRTBasis of c0, c1;
+ *     FastExpandCRTBasisPloverQ of d0, d1 (dcrtpoly-impl.h:1413-1466: INTT,
+ *     approximate switch through q_to_r_neg, exact switch R -> Q replacing the
+ *     Q towers, NTT); the tensor product, INTT, ScaleAndRound to Q (out_is_q = 1).
+ * Scratch comes from the context's stream-ordered pool; no call synchronises. */
+enum {
+    OFHE_BFV_HPS = 0,
+    OFHE_BFV_HPSPOVERQ = 1
+};
+typedef struct ofhe_bfv_mult_s* ofhe_bfv_mult_t;
+int ofhe_hip_bfv_mult_create(ofhe_ctx_t ctx, int technique, ofhe_plan_t plan_q, ofhe_plan_t plan_r,
+                             ofhe_plan_t plan_qr, ofhe_bconv_t q_to_r, ofhe_bconv_t r_to_q, ofhe_bconv_t q_to_r_neg,
+                             ofhe_scale_round_t scale_round, ofhe_bfv_mult_t* handle);
+int ofhe_hip_bfv_mult_destroy(ofhe_bfv_mult_t handle);
+int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t handle, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
+                           const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
+                           void* stream);
 
 /* ---- multi-GPU: evaluation-key broadcast over RCCL (xGMI) ----
  * the path shards by ciphertext batch with no exchange;

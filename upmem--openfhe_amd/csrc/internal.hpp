@@ -15,6 +15,7 @@
 #include "../../include/ofhe_hip.h"
 #include "eltwise_kernels.hpp"
 #include "bconv_mma.hpp"
+#include "bfv_kernels.hpp"
 
 namespace ofhe {
 typedef unsigned __int128 u128;
@@ -126,6 +127,11 @@ inline hipError_t upload_blocking(void* dst, const void* src, size_t bytes) {
 // ApproxSwitchCRTBasis launch (strides and output gap from A)
 int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);
 
+// SwitchCRTBasis (exact, bfv_kernels.hpp) launch with b's tables; strides and
+// output gap from A (a copy of b->args with the caller's strides).  The
+// alphaQModp / qInv tables are built and uploaded on b's first exact call.
+int switch_exact_run(ofhe_bconv_t b, const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);
+
 }  // namespace ofhe
 
 struct ofhe_ctx_s {
@@ -139,6 +145,33 @@ struct ofhe_ctx_s {
     std::mutex blocks_mu;
     std::set<void*> async_blocks;
 };
+
+namespace ofhe {
+// Stream-ordered scratch from the context's pool: freed on the stream when the
+// owner goes out of scope.
+struct Scratch {
+    void* p = nullptr;
+    hipStream_t s = nullptr;
+    int alloc(size_t bytes, hipStream_t st, ofhe_ctx_t ctx) {
+        s = st;
+        hipError_t e = ctx->pool ? hipMallocFromPoolAsync(&p, bytes ? bytes : 8, ctx->pool, st)
+                                 : hipMallocAsync(&p, bytes ? bytes : 8, st);
+        if (e != hipSuccess) return fail(OFHE_ERR_NOMEM, std::string("scratch: ") + hipGetErrorString(e));
+        return OFHE_OK;
+    }
+    u64* w() const { return (u64*)p; }
+    ~Scratch() {
+        if (p) (void)hipFreeAsync(p, s);
+    }
+};
+
+// `rows` rows of `words` words, device to device, with row strides in words
+inline int copy_rows(u64* dst, u64 dstride, const u64* src, u64 sstride, u64 words, u32 rows, hipStream_t s) {
+    if (!words || !rows) return OFHE_OK;
+    HIPCHK(hipMemcpy2DAsync(dst, dstride * 8, src, sstride * 8, words * 8, rows, hipMemcpyDeviceToDevice, s));
+    return OFHE_OK;
+}
+}  // namespace ofhe
 
 enum { SPLIT_COLS = 0, SPLIT_T8 = 1, SPLIT_T9 = 2, SPLIT_T8B9 = 3 };
 // stages of the block pass (its inverse groups have 2^block_stages elements)
@@ -195,4 +228,10 @@ struct ofhe_bconv_s {
     std::map<std::vector<ofhe::u64>, ofhe::u64*> tabs;
     // k_bconv_cols in ofhe_hip_approx_mod_up / _down (options.separate_cols = 0)
     bool bcols = true;
+    // ofhe_hip_switch_crt_basis: host copies of the moduli, and the exact
+    // switch's tables (qInv, alphaQModp) derived from them on the first exact
+    // call (under tab_mu), uploaded once and kept until destroy
+    std::vector<ofhe::u64> hq, hp;
+    void* d_exact = nullptr;
+    ofhe::ExactArgs exact{};
 };

@@ -82,30 +82,6 @@ int sub_scale(const TowerScalar* d, const u64* x, const u64* y, u64* out, u64 xs
     return post_launch();
 }
 
-// Stream-ordered scratch from the context's pool: freed on the stream when the
-// owner goes out of scope.
-struct Scratch {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    int alloc(size_t bytes, hipStream_t st, ofhe_ctx_t ctx) {
-        s = st;
-        hipError_t e = ctx->pool ? hipMallocFromPoolAsync(&p, bytes ? bytes : 8, ctx->pool, st)
-                                 : hipMallocAsync(&p, bytes ? bytes : 8, st);
-        if (e != hipSuccess) return fail(OFHE_ERR_NOMEM, std::string("scratch: ") + hipGetErrorString(e));
-        return OFHE_OK;
-    }
-    u64* w() const { return (u64*)p; }
-    ~Scratch() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
-int copy_rows(u64* dst, u64 dstride, const u64* src, u64 sstride, u64 words, u32 rows, hipStream_t s) {
-    if (!words || !rows) return OFHE_OK;
-    HIPCHK(hipMemcpy2DAsync(dst, dstride * 8, src, sstride * 8, words * 8, rows, hipMemcpyDeviceToDevice, s));
-    return OFHE_OK;
-}
-
 // ApproxModDown core shared by the generic entry point and the key-switch
 // engine.  x: [batch][Q+P] (xstride), the P part at x + Q*N; plan towers
 // pq0.. for Q and pp0.. for P (both in `plan_q` / `plan_p`).

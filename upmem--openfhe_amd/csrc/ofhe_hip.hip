@@ -1185,6 +1185,8 @@ int ofhe_hip_bconv_create_ex(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, ui
     A.mm_tpc = mm_tpc;
     A.mm_spq = mm_spq ? 1 : 0;
     A.kernel = opt.kernel;
+    b->hq.assign(q, q + size_q);
+    b->hp.assign(p, p + size_p);
     *out = b;
     return OFHE_OK;
 }
@@ -1193,6 +1195,7 @@ int ofhe_hip_bconv_destroy(ofhe_bconv_t b) {
     if (!b) return fail(OFHE_ERR_ARG, "bconv is NULL");
     if (b->ctx) (void)hipSetDevice(b->ctx->device);
     (void)hipFree(b->d_mem);
+    (void)hipFree(b->d_exact);
     for (auto& kv : b->tabs) (void)hipFree(kv.second);
     delete b;
     return OFHE_OK;
@@ -1279,7 +1282,90 @@ int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t
         hipLaunchKernelGGL((k_bconv<8>), dim3((u32)blocks), dim3(256), 0, s, A, x, out, batch);
     return post_launch();
 }
+
+// The exact switch's tables (CryptoParametersBFVRNS::PrecomputeCRTTables):
+// qInv[i] = 1.0 / double(q_i) (bfvrns-cryptoparameters.cpp:270-273, 441-444)
+// and alphaQModp[a][j] = (Q mod p_j) a mod p_j, a = 0 .. size_q (343-350,
+// 418-424), from the handle's moduli; uploaded once into memory no launch has
+// read yet (upload_blocking), so later calls only read the cached pointers.
+static int exact_tables(ofhe_bconv_t b) {
+    std::lock_guard<std::mutex> lk(b->tab_mu);
+    if (b->d_exact) return OFHE_OK;
+    const u32 sq = (u32)b->hq.size(), sp = (u32)b->hp.size();
+    std::vector<u64> h(sq + (size_t)(sq + 1) * sp);
+    for (u32 i = 0; i < sq; i++) {
+        const double inv = 1. / static_cast<double>(b->hq[i]);
+        std::memcpy(&h[i], &inv, sizeof(double));
+    }
+    for (u32 j = 0; j < sp; j++) {
+        const u64 pj = b->hp[j];
+        u64 qmod = 1 % pj;
+        for (u32 i = 0; i < sq; i++) qmod = mulmod(qmod, b->hq[i] % pj, pj);
+        for (u32 a = 0; a <= sq; a++) h[sq + (size_t)a * sp + j] = mulmod(qmod, a % pj, pj);
+    }
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, h.size() * sizeof(u64)));
+    hipError_t e = upload_blocking(d, h.data(), h.size() * sizeof(u64));
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(OFHE_ERR_HIP, std::string("exact switch tables: ") + hipGetErrorString(e));
+    }
+    b->exact.qinv = reinterpret_cast<const double*>(d);
+    b->exact.aq = reinterpret_cast<const u64*>(d) + sq;
+    b->d_exact = d;
+    return OFHE_OK;
+}
+
+// SwitchCRTBasis: one launch.  The kernel choice mirrors bconv_run's (matrix
+// cores for <= 64 sources and N >= 32 unless the handle asks for LIMB / WIDE).
+int switch_exact_run(ofhe_bconv_t b, const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s) {
+    if (A.lazy_out) return fail(OFHE_ERR_ARG, "internal: the exact switch has canonical outputs only");
+    RCCHK(exact_tables(b));
+    const ExactArgs E = b->exact;
+    const u64 total = (u64)batch << A.log_n;
+    const u64 blocks = (total + 255) / 256;
+    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
+    const bool generic = A.kernel == OFHE_BCONV_KERNEL_WIDE, limb = A.kernel == OFHE_BCONV_KERNEL_LIMB;
+    if (OFHE_BCONV_MMA && A.mm_tab && A.log_n >= 5 && !generic && !limb) {
+        const u64 groups = total >> 5;
+        const u32 wpb = BCONV_MMA_THREADS / 64;
+        const u32 chunks = (A.mm_tiles + A.mm_tpc - 1) / A.mm_tpc;
+        u64 gx = (groups + wpb - 1) / wpb;
+        u64 cap = 256ull * BCONV_MMA_BLOCKS_PER_CU / chunks;
+        if (cap < 1) cap = 1;
+        if (gx > cap) gx = cap;
+        const size_t lds = bconv_mma_lds(A.mm_tpc, A.mm_ks);
+        const dim3 grid((u32)gx, chunks);
+        switch (A.mm_ks) {
+#define SX_CASE(K)                                                                                              \
+    case K:                                                                                                     \
+        if (A.mm_spq)                                                                                           \
+            hipLaunchKernelGGL((k_switch_mma<K, true>), grid, dim3(BCONV_MMA_THREADS), lds, s, A, E, x, out, batch);  \
+        else                                                                                                    \
+            hipLaunchKernelGGL((k_switch_mma<K, false>), grid, dim3(BCONV_MMA_THREADS), lds, s, A, E, x, out, batch); \
+        break;
+            SX_CASE(1) SX_CASE(2) SX_CASE(3) SX_CASE(4) SX_CASE(5) SX_CASE(6) SX_CASE(7) SX_CASE(8)
+            SX_CASE(10) SX_CASE(12) SX_CASE(14) SX_CASE(16)
+#undef SX_CASE
+            default:
+                return fail(OFHE_ERR_STATE, "bconv: bad K-step count");
+        }
+        return post_launch();
+    }
+    if (A.size_q <= BCONV_LIMB_QMAX && !generic)
+        hipLaunchKernelGGL((k_switch_limb<BCONV_PT>), dim3((u32)blocks), dim3(256), 0, s, A, E, x, out, batch);
+    else
+        hipLaunchKernelGGL((k_switch_wide<8>), dim3((u32)blocks), dim3(256), 0, s, A, E, x, out, batch);
+    return post_launch();
+}
 }  // namespace ofhe
+
+int ofhe_hip_switch_crt_basis(ofhe_bconv_t b, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream) {
+    if (!b || !b->ctx) return fail(OFHE_ERR_STATE, "bconv is NULL or destroyed");
+    if (!x || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
+    HIPCHK(hipSetDevice(b->ctx->device));
+    return switch_exact_run(b, b->args, x, out, batch, pick(stream));
+}
 
 int ofhe_hip_approx_switch_crt_basis(ofhe_bconv_t b, const uint64_t* x, uint64_t* out, uint32_t batch,
                                      void* stream) {

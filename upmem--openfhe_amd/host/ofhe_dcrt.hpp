@@ -16,6 +16,10 @@
 //                                (PimData.h:16-21): towers gathered from
 //                                separate host vectors into pinned memory, one
 //                                transfer each way
+//   BaseConverter::SwitchCRTBasis, ExpandCRTBasis, ScaleAndRound, BfvMult
+//                             <- the BFV (HPS / HPSPOVERQ) multiplication steps
+//                                (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955,
+//                                bfvrns-leveledshe.cpp:168-408)
 //   KsCache / KeyCache        <- the per-parameter-set HYBRID tables
 //                                (rns-cryptoparameters.cpp:72-345) and the
 //                                evaluation keys kept resident on the device
@@ -781,6 +785,16 @@ public:
         check(ofhe_hip_approx_switch_crt_basis(h_, x.data(), out.data(), x.Batch(), nullptr), "ApproxSwitchCRTBasis");
         return out;
     }
+    // SwitchCRTBasis (dcrtpoly-impl.h:1178-1230), the exact switch with the
+    // floating-point overflow count: this converter must hold the true CRT
+    // tables (QHatInvModq, QHatModp); alphaQModp and qInv are derived from its
+    // moduli inside the backend.
+    DCRTPolyHip SwitchCRTBasis(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP) const {
+        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("SwitchCRTBasis: COEFFICIENT form expected");
+        DCRTPolyHip out(paramsP, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_switch_crt_basis(h_, x.data(), out.data(), x.Batch(), nullptr), "SwitchCRTBasis");
+        return out;
+    }
 
     ofhe_bconv_t handle() const { return h_; }
 
@@ -800,6 +814,118 @@ inline DCRTPolyHip ApproxModUp(const DCRTPolyHip& x, const std::shared_ptr<DCRTP
           "ApproxModUp");
     return out;
 }
+
+// ExpandCRTBasis with resultFormat = EVALUATION (dcrtpoly-impl.h:1311-1358):
+// x over Q (either format) -> Q|P in EVALUATION form through the exact switch;
+// q_to_p holds the true CRT tables of Q -> P.
+inline DCRTPolyHip ExpandCRTBasis(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP,
+                                  const std::shared_ptr<DCRTParams>& paramsQP, const BaseConverter& q_to_p) {
+    const auto& Q = x.GetParams();
+    if (paramsQP->Towers() != Q->Towers() + paramsP->Towers()) throw math_error("ExpandCRTBasis: paramsQP size");
+    DCRTPolyHip out(paramsQP, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
+    check(ofhe_hip_expand_crt_basis(Q->plan(), paramsP->plan(), q_to_p.handle(), x.GetFormat() == Format::EVALUATION,
+                                    x.data(), out.data(), x.Batch(), nullptr),
+          "ExpandCRTBasis");
+    return out;
+}
+
+// ScaleAndRound, DCRTPoly -> DCRTPoly (dcrtpoly-impl.h:1876-1955): x over Q|P
+// (COEFFICIENT) -> P (outIsQ = false, HPS) or Q (outIsQ = true, HPSPOVERQ).
+// tOSHatInvModsDivsModo is the reference's vector of rows (one per output
+// tower, sizeI + 1 entries), tOSHatInvModsDivsFrac its vector of doubles.
+class ScaleAndRound {
+public:
+    ScaleAndRound(const DCRTParams& Q, const DCRTParams& P, bool outIsQ,
+                  const std::vector<std::vector<uint64_t>>& tOSHatInvModsDivsModo,
+                  const std::vector<double>& tOSHatInvModsDivsFrac)
+        : out_is_q_(outIsQ) {
+        const size_t si = outIsQ ? P.Towers() : Q.Towers(), so = outIsQ ? Q.Towers() : P.Towers();
+        if (tOSHatInvModsDivsModo.size() != so || tOSHatInvModsDivsFrac.size() != si)
+            throw math_error("ScaleAndRound: table sizes do not match the bases");
+        std::vector<uint64_t> flat;
+        for (const auto& row : tOSHatInvModsDivsModo) {
+            if (row.size() != si + 1) throw math_error("ScaleAndRound: table row size");
+            flat.insert(flat.end(), row.begin(), row.end());
+        }
+        check(ofhe_hip_scale_round_create(Q.manager()->ctx(), Q.LogN(), (uint32_t)Q.Towers(), (uint32_t)P.Towers(),
+                                          Q.Moduli().data(), P.Moduli().data(), outIsQ ? 1 : 0, flat.data(),
+                                          tOSHatInvModsDivsFrac.data(), &h_),
+              "ScaleAndRound");
+    }
+    ~ScaleAndRound() {
+        if (h_) ofhe_hip_scale_round_destroy(h_);
+    }
+    ScaleAndRound(const ScaleAndRound&) = delete;
+    ScaleAndRound& operator=(const ScaleAndRound&) = delete;
+    DCRTPolyHip operator()(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsOutput) const {
+        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("ScaleAndRound: COEFFICIENT form expected");
+        DCRTPolyHip out(paramsOutput, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_scale_and_round(h_, x.data(), out.data(), x.Batch(), nullptr), "ScaleAndRound");
+        return out;
+    }
+    bool OutIsQ() const { return out_is_q_; }
+    ofhe_scale_round_t handle() const { return h_; }
+
+private:
+    ofhe_scale_round_t h_ = nullptr;
+    bool out_is_q_;
+};
+
+// LeveledSHEBFVRNS::EvalMult (bfvrns-leveledshe.cpp:168-408), HPS or HPSPOVERQ,
+// for two 2-element ciphertexts, from the outputs of the reference's getters
+// as vectors: QHatInvModq / QHatModr ([sizeQ][sizeR] flattened), RHatInvModr /
+// RHatModq ([sizeR][sizeQ] flattened), the ScaleAndRound tables, and for
+// HPSPOVERQ mNegRlQHatInvModq / qInvModr ([sizeQ][sizeR] flattened).
+class BfvMult {
+public:
+    enum Technique { HPS = OFHE_BFV_HPS, HPSPOVERQ = OFHE_BFV_HPSPOVERQ };
+    BfvMult(Technique tech, std::shared_ptr<DCRTParams> Q, std::shared_ptr<DCRTParams> R,
+            std::shared_ptr<DCRTParams> QR, const std::vector<uint64_t>& QHatInvModq,
+            const std::vector<uint64_t>& QHatModr, const std::vector<uint64_t>& RHatInvModr,
+            const std::vector<uint64_t>& RHatModq, const std::vector<std::vector<uint64_t>>& tSHatInvModsDivsModo,
+            const std::vector<double>& tSHatInvModsDivsFrac, const std::vector<uint64_t>& mNegRlQHatInvModq = {},
+            const std::vector<uint64_t>& qInvModr = {})
+        : Q_(std::move(Q)), R_(std::move(R)), QR_(std::move(QR)), q_to_r_(*Q_, *R_, QHatInvModq, QHatModr),
+          r_to_q_(*R_, *Q_, RHatInvModr, RHatModq),
+          sr_(*Q_, *R_, tech == HPSPOVERQ, tSHatInvModsDivsModo, tSHatInvModsDivsFrac) {
+        if (tech == HPSPOVERQ) neg_.reset(new BaseConverter(*Q_, *R_, mNegRlQHatInvModq, qInvModr));
+        check(ofhe_hip_bfv_mult_create(Q_->manager()->ctx(), (int)tech, Q_->plan(), R_->plan(), QR_->plan(),
+                                       q_to_r_.handle(), r_to_q_.handle(), neg_ ? neg_->handle() : nullptr,
+                                       sr_.handle(), &h_),
+              "BfvMult");
+    }
+    ~BfvMult() {
+        if (h_) ofhe_hip_bfv_mult_destroy(h_);
+    }
+    BfvMult(const BfvMult&) = delete;
+    BfvMult& operator=(const BfvMult&) = delete;
+    // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
+    std::vector<DCRTPolyHip> EvalMult(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
+                                      const DCRTPolyHip& d1) const {
+        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
+            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
+                v->Batch() != c0.Batch())
+                throw math_error("BfvMult::EvalMult: EVALUATION-form ciphertexts over Q of one batch expected");
+        std::vector<DCRTPolyHip> out;
+        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_bfv_eval_mult(h_, c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(), out[1].data(),
+                                     out[2].data(), c0.Batch(), nullptr),
+              "BfvMult::EvalMult");
+        return out;
+    }
+    const BaseConverter& QToR() const { return q_to_r_; }
+    const BaseConverter& RToQ() const { return r_to_q_; }
+    const BaseConverter* QToRNeg() const { return neg_.get(); }  // null for HPS
+    const ScaleAndRound& Scale() const { return sr_; }
+    ofhe_bfv_mult_t handle() const { return h_; }
+
+private:
+    std::shared_ptr<DCRTParams> Q_, R_, QR_;
+    BaseConverter q_to_r_, r_to_q_;
+    ScaleAndRound sr_;
+    std::unique_ptr<BaseConverter> neg_;
+    ofhe_bfv_mult_t h_ = nullptr;
+};
 
 // ApproxModDown (dcrtpoly-impl.h:1134-1175): x over Q|P (EVALUATION) -> Q.
 inline DCRTPolyHip ApproxModDown(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsQ,

@@ -16,6 +16,11 @@ Host-side mirror of the reference's offload interface for the hot path:
   ``fast_rotation`` / ``fast_rotation_ext`` ~ ``EvalFastRotation``
   (base-leveledshe.cpp:471-513) / ``EvalFastRotationExt``
   (ckksrns-leveledshe.cpp:402-457) for many keys over one digit set.
+* ``BaseConverter.switch_exact`` / ``expand_crt_basis`` / ``ScaleRound`` / ``BfvMult`` ~
+  ``DCRTPolyImpl::SwitchCRTBasis`` / ``ExpandCRTBasis`` / ``ScaleAndRound``
+  (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955) and ``LeveledSHEBFVRNS::EvalMult``
+  for HPS / HPSPOVERQ (bfvrns-leveledshe.cpp:168-408); their tables come from
+  ``bfv_tables.py``.
 * ``switch_modulus`` / ``NTTPlan.automorphism`` ~ ``NativeVectorT::SwitchModulus``
   (mubintvecnat.cpp:111-136) / ``PolyImpl::AutomorphismTransform`` (poly-impl.h:312-365).
 
@@ -133,6 +138,17 @@ _SIGS = {
     "ofhe_hip_bv_core": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp,
                                         ctypes.c_uint32, _vp]),
     "ofhe_hip_eval_mult_core": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_switch_crt_basis": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_expand_crt_basis": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_scale_round_create": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u64p,
+                                                   _u64p, ctypes.c_int, _u64p, ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(_vp)]),
+    "ofhe_hip_scale_round_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_scale_and_round": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_mult_create": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                ctypes.POINTER(_vp)]),
+    "ofhe_hip_bfv_mult_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_bfv_eval_mult": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_comm_unique_id": (ctypes.c_int, [_vp]),
     "ofhe_hip_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "ofhe_hip_comm_destroy": (ctypes.c_int, [_vp]),
@@ -476,6 +492,11 @@ class BaseConverter:
     def switch(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_approx_switch_crt_basis(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
 
+    def switch_exact(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        """DCRTPolyImpl::SwitchCRTBasis (dcrtpoly-impl.h:1178-1230): the exact switch with the
+        floating-point overflow count; the converter must hold the true CRT tables."""
+        _check(lib().ofhe_hip_switch_crt_basis(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
 
 def switch_modulus(ctx: Context, src: int, dst: int, n: int, old_q: int, new_q: int, stream: int = 0) -> None:
     """NativeVectorT::SwitchModulus on n words of device memory."""
@@ -488,6 +509,87 @@ def approx_mod_up(plan_q: NTTPlan, plan_p: NTTPlan, q_to_p: BaseConverter, eval_
     """ApproxModUp: x [batch][Q][N] -> out [batch][Q+P][N] (evaluation form)."""
     _check(lib().ofhe_hip_approx_mod_up(plan_q.handle, plan_p.handle, q_to_p._h, 1 if eval_form else 0, _vp(x),
                                         _vp(out), int(batch), _vp(stream or None)))
+
+
+def expand_crt_basis(plan_q: NTTPlan, plan_p: NTTPlan, q_to_p: BaseConverter, eval_form: bool, x: int, out: int,
+                     batch: int = 1, stream: int = 0) -> None:
+    """ExpandCRTBasis (dcrtpoly-impl.h:1311-1358, resultFormat = EVALUATION): x [batch][Q][N] -> out
+    [batch][Q+P][N] (evaluation form) through the exact switch."""
+    _check(lib().ofhe_hip_expand_crt_basis(plan_q.handle, plan_p.handle, q_to_p._h, 1 if eval_form else 0, _vp(x),
+                                           _vp(out), int(batch), _vp(stream or None)))
+
+
+class ScaleRound:
+    """DCRTPolyImpl::ScaleAndRound, DCRTPoly -> DCRTPoly (dcrtpoly-impl.h:1876-1955).  x is
+    [batch][len(q) + len(p)][N], Q towers first, coefficient form; out_is_q = False (HPS) sums the Q
+    towers into the P basis, True (HPSPOVERQ) the P towers into the Q basis.  int_table: size_o rows of
+    size_i + 1 words (tOSHatInvModsDivsModo), frac: size_i doubles (tOSHatInvModsDivsFrac)."""
+
+    def __init__(self, ctx: Context, log_n: int, q: Sequence[int], p: Sequence[int], out_is_q: bool,
+                 int_table: Sequence[Sequence[int]], frac: Sequence[float]):
+        self.ctx, self.log_n = ctx, int(log_n)
+        self.size_q, self.size_p, self.out_is_q = len(q), len(p), bool(out_is_q)
+        si, so = (self.size_p, self.size_q) if out_is_q else (self.size_q, self.size_p)
+        if len(int_table) != so or any(len(r) != si + 1 for r in int_table) or len(frac) != si:
+            raise MathError("table sizes do not match the bases")
+        self.size_i, self.size_o = si, so
+        h = _vp()
+        fr = (ctypes.c_double * si)(*[float(v) for v in frac])
+        _check(lib().ofhe_hip_scale_round_create(ctx.handle, self.log_n, self.size_q, self.size_p, _arr(q), _arr(p),
+                                                 1 if out_is_q else 0, _arr([v for r in int_table for v in r]), fr,
+                                                 ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(lib().ofhe_hip_scale_round_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_scale_and_round(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+
+BFV_HPS, BFV_HPSPOVERQ = range(2)
+
+
+class BfvMult:
+    """LeveledSHEBFVRNS::EvalMult (bfvrns-leveledshe.cpp:168-408) for two 2-element ciphertexts, technique
+    HPS or HPSPOVERQ, composed from the caller's handles (kept alive by this object).  q_to_r_neg (the
+    mNegRlQHatInvModq / qInvModr converter) is None for HPS."""
+
+    def __init__(self, ctx: Context, technique: int, plan_q: NTTPlan, plan_r: NTTPlan, plan_qr: NTTPlan,
+                 q_to_r: BaseConverter, r_to_q: BaseConverter, q_to_r_neg: Optional[BaseConverter],
+                 scale_round: ScaleRound):
+        self._parts = (ctx, plan_q, plan_r, plan_qr, q_to_r, r_to_q, q_to_r_neg, scale_round)
+        h = _vp()
+        _check(lib().ofhe_hip_bfv_mult_create(ctx.handle, int(technique), plan_q.handle, plan_r.handle,
+                                              plan_qr.handle, q_to_r._h, r_to_q._h,
+                                              None if q_to_r_neg is None else q_to_r_neg._h, scale_round._h,
+                                              ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(lib().ofhe_hip_bfv_mult_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval_mult(self, c0: int, c1: int, d0: int, d1: int, out0: int, out1: int, out2: int, batch: int = 1,
+                  stream: int = 0) -> None:
+        """Inputs [batch][Q][N] evaluation form; outputs [batch][Q][N] coefficient form."""
+        _check(lib().ofhe_hip_bfv_eval_mult(self._h, _vp(c0), _vp(c1), _vp(d0), _vp(d1), _vp(out0), _vp(out1),
+                                            _vp(out2), int(batch), _vp(stream or None)))
 
 
 def approx_mod_down(plan_q: NTTPlan, plan_p: NTTPlan, p_to_q: BaseConverter, p_inv_modq: Sequence[int], t: int,
