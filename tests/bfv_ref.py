@@ -15,6 +15,12 @@ fused multiply-add chain would compute (each a*b+c exact, rounded once), kept
 for the sensitivity check of the tests.
 
 Polynomials are uint64 arrays [batch][towers][n].
+
+``fast=True`` (switch_crt_basis, scale_and_round and their callers) computes the same residues with
+64-bit words in numpy instead of Python integers, for the shapes of 2^16 and 2^17 coefficients whose
+object arrays take seconds: every product c x mod m is Shoup's (floor(x floor(c 2^64 / m) / 2^64) as
+the quotient, one correction), sums are taken mod m term by term.  The double sums are the same code.
+tests/test_bfv_oracle.py checks the two paths against each other.
 """
 import json
 import os
@@ -31,6 +37,32 @@ def obj(a):
 
 def u64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=object).astype(np.uint64))
+
+
+# ---- 64-bit words (fast = True) -----------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _mulhi(a, b):
+    """floor(a b / 2^64) for a uint64 array a and an integer 0 <= b < 2^64, from 32-bit halves"""
+    b0, b1 = np.uint64(b & 0xFFFFFFFF), np.uint64(b >> 32)
+    a0, a1 = a & _M32, a >> _S32
+    p01, p10 = a0 * b1, a1 * b0
+    mid = ((a0 * b0) >> _S32) + (p01 & _M32) + (p10 & _M32)
+    return a1 * b1 + (p01 >> _S32) + (p10 >> _S32) + (mid >> _S32)
+
+
+def mulmod_const(a, c, m):
+    """a c mod m, canonical, for a uint64 array a (any words), integers 0 <= c < m < 2^63"""
+    c, m = int(c) % int(m), int(m)
+    r = a * np.uint64(c) - _mulhi(a, (c << 64) // m) * np.uint64(m)  # wraps mod 2^64; in [0, 2 m)
+    return np.where(r >= np.uint64(m), r - np.uint64(m), r)
+
+
+def _addmod(a, b, m):
+    s = a + b
+    return np.where(s >= np.uint64(m), s - np.uint64(m), s)
 
 
 # ---- SwitchCRTBasis ---------------------------------------------------------------
@@ -67,9 +99,26 @@ def nu_switch_fused(ys, q):
     return nu
 
 
-def switch_crt_basis(x, q, p, want_alpha=False):
+def _switch_crt_basis_fast(x, q, p):
+    hinv = BT.hat_inv(q)
+    ys = [mulmod_const(x[:, i, :], hinv[i], q[i]) for i in range(len(q))]
+    alpha = nu_switch(ys, q).astype(np.int64)
+    hm, aq = BT.hat_mod(q, p), BT.alpha_mod(q, p)
+    out = np.empty((x.shape[0], len(p), x.shape[2]), dtype=np.uint64)
+    for j, pj in enumerate(p):
+        cur = np.zeros(ys[0].shape, dtype=np.uint64)
+        for i in range(len(q)):
+            cur = _addmod(cur, mulmod_const(ys[i], hm[i][j], pj), pj)
+        sub = np.array([aq[a][j] for a in range(len(q) + 1)], dtype=np.uint64)[alpha]
+        out[:, j, :] = np.where(cur >= sub, cur - sub, cur + np.uint64(pj) - sub)
+    return out
+
+
+def switch_crt_basis(x, q, p, want_alpha=False, fast=False):
     """x [batch][len(q)][n] -> [batch][len(p)][n] (1178-1230)"""
     x = np.asarray(x, dtype=np.uint64)
+    if fast:
+        return _switch_crt_basis_fast(x, q, p)
     ys = switch_ys(x, q)
     alpha = nu_switch(ys, q).astype(np.int64)  # static_cast<usint>(nu), 1209
     hm, aq = BT.hat_mod(q, p), BT.alpha_mod(q, p)
@@ -91,7 +140,7 @@ def nu_scale(xin, frac):
     return nu
 
 
-def scale_and_round(x, q, p, out_is_q, table, frac, want_nu=False):
+def scale_and_round(x, q, p, out_is_q, table, frac, want_nu=False, fast=False):
     """x [batch][len(q) + len(p)][n], Q towers first (1876-1955); both alpha branches are
     floor(nu) mod o_j, taken here with exact integers"""
     x = np.asarray(x, dtype=np.uint64)
@@ -99,6 +148,15 @@ def scale_and_round(x, q, p, out_is_q, table, frac, want_nu=False):
     xin, xown, outs = (x[:, sq:, :], x[:, :sq, :], q) if out_is_q else (x[:, :sq, :], x[:, sq:, :], p)
     si = xin.shape[1]
     nu = nu_scale(xin, frac)
+    if fast and nu.max() < 2.0 ** 63:  # floor(nu) fits a word
+        floor_nu = nu.astype(np.uint64)
+        out = np.empty((x.shape[0], len(outs), x.shape[2]), dtype=np.uint64)
+        for j, oj in enumerate(outs):
+            cur = mulmod_const(xown[:, j, :], table[j][si], oj)
+            for i in range(si):
+                cur = _addmod(cur, mulmod_const(xin[:, i, :], table[j][i], oj), oj)
+            out[:, j, :] = _addmod(cur, floor_nu % np.uint64(oj), oj)
+        return (out, nu) if want_nu else out
     alpha = np.array([int(v) for v in nu.reshape(-1)], dtype=object).reshape(nu.shape)
     out = np.empty((x.shape[0], len(outs), x.shape[2]), dtype=np.uint64)
     xi = [obj(xin[:, i, :]) for i in range(si)]
@@ -109,11 +167,11 @@ def scale_and_round(x, q, p, out_is_q, table, frac, want_nu=False):
 
 
 # ---- ExpandCRTBasis / FastExpandCRTBasisPloverQ ---------------------------------
-def expand_crt_basis(O, x, q, r, tb_q, tb_r, eval_form):
+def expand_crt_basis(O, x, q, r, tb_q, tb_r, eval_form, fast=False):
     """-> [batch][Q+R][n] evaluation form (1311-1358, resultFormat = EVALUATION)"""
     x = np.asarray(x, dtype=np.uint64)
     coef = O.ntt_inv(x, tb_q) if eval_form else x
-    part_r = O.ntt_fwd(switch_crt_basis(coef, q, r), tb_r)
+    part_r = O.ntt_fwd(switch_crt_basis(coef, q, r, fast=fast), tb_r)
     part_q = x if eval_form else O.ntt_fwd(x, tb_q)
     return np.concatenate([part_q, part_r], axis=1)
 
@@ -128,12 +186,12 @@ def approx_switch_with(O, x, q, p, c, d):
     return np.stack([O.approx_switch_crt_basis(np.ascontiguousarray(xb), q, p, pre) for xb in x])
 
 
-def fast_expand_p_over_q(O, x, T):
+def fast_expand_p_over_q(O, x, T, fast=False):
     """x [batch][Q][n] coefficient form -> [batch][Q+R][n] coefficient form (1413-1466): the R part
     by the approximate switch with mNegRlQHatInvModq / qInvModr, the Q part replaced by its exact
     switch back"""
     part_r = approx_switch_with(O, np.asarray(x, dtype=np.uint64), T.q, T.r, T.neg_r_q_hat_inv_modq, T.q_inv_modr)
-    part_q = switch_crt_basis(part_r, T.r, T.q)
+    part_q = switch_crt_basis(part_r, T.r, T.q, fast=fast)
     return np.concatenate([part_q, part_r], axis=1)
 
 
@@ -147,22 +205,22 @@ class Ring:
         self.tb_qr = O.Tables(self.n, list(q) + list(r), list(rq) + list(rr))
 
 
-def eval_mult(O, T, ring, c0, c1, d0, d1):
+def eval_mult(O, T, ring, c0, c1, d0, d1, fast=False):
     """(out0, out1, out2), [batch][Q][n] coefficient form, of two evaluation-form ciphertexts
     (bfvrns-leveledshe.cpp:168-408), technique T.technique"""
     q, r, qr = T.q, T.r, T.q + T.r
-    ex = lambda v: expand_crt_basis(O, v, q, r, ring.tb_q, ring.tb_r, True)  # noqa: E731
+    ex = lambda v: expand_crt_basis(O, v, q, r, ring.tb_q, ring.tb_r, True, fast)  # noqa: E731
     e = [ex(c0), ex(c1)]
     if T.technique == BT.HPS:
         e += [ex(d0), ex(d1)]
     else:
-        e += [O.ntt_fwd(fast_expand_p_over_q(O, O.ntt_inv(v, ring.tb_q), T), ring.tb_qr) for v in (d0, d1)]
+        e += [O.ntt_fwd(fast_expand_p_over_q(O, O.ntt_inv(v, ring.tb_q), T, fast), ring.tb_qr) for v in (d0, d1)]
     mul = lambda a, b: O.eltwise("mul", a, b, qr)  # noqa: E731
     prods = [mul(e[0], e[2]), O.eltwise("add", mul(e[0], e[3]), mul(e[1], e[2]), qr), mul(e[1], e[3])]
     outs = []
     for pr in prods:
-        sr = scale_and_round(O.ntt_inv(pr, ring.tb_qr), q, r, T.out_is_q, T.sr_table, T.sr_frac)
-        outs.append(switch_crt_basis(sr, r, q) if T.technique == BT.HPS else sr)
+        sr = scale_and_round(O.ntt_inv(pr, ring.tb_qr), q, r, T.out_is_q, T.sr_table, T.sr_frac, fast=fast)
+        outs.append(switch_crt_basis(sr, r, q, fast=fast) if T.technique == BT.HPS else sr)
     return outs
 
 
@@ -297,6 +355,108 @@ def switch_case(O, log_n, sq, sp):
             m, _ = O.moduli_chain(log_n, sq + sp)
         q, p = m[:sq], m[sq:]
         _switch_cases[key] = (q, p) + switch_inputs(q, 1 << log_n, SWITCH_BATCH, 1000 + 31 * sq + sp)
+    return _switch_cases[key]
+
+
+# ---- the matrix-core kernel's K-step counts, target chunks and grid cap -------------------------
+# (log_n, size_q, size_p): one case per instantiated K-step count of k_switch_mma that SWITCH_CASES
+# leaves out (KS = ceil(size_q / 4), rounded up to even above 8: 3, 6, 7, 8 and the WIDE combine's 10,
+# 12, 14, 16), two of them with more targets than one block's LDS image holds (blockIdx.y > 0).
+# tests/test_bfv_oracle.py restates the host's K-step / chunk arithmetic and asserts this table.
+SWITCH_CASES_MMA = [(5, 12, 3), (5, 24, 5), (5, 28, 2), (6, 32, 29), (5, 40, 3), (5, 48, 2), (5, 56, 2), (6, 64, 13)]
+# the cases on a generic_moduli chain of mixed 22-60-bit towers (no special-prime reduction); the
+# others have 60-bit towers of the form 2^60 - d
+SWITCH_MMA_MIXED = {(5, 24, 5): 6, (5, 48, 2): 12}  # case -> its K-step count
+# the grid cap: 1024 blocks of 256 coefficients against a cap of 768, so the group loop's second trip
+# is a partial one
+SWITCH_CAP_CASE = (16, 2, 3)
+SWITCH_CAP_BATCH = 4
+EXTREME = 3  # kinds: the three columns of extreme_columns
+DIGITS_MAX, DIGITS_MIN = 0x0F7F7F7F7F7F7F7F, 0x0080808080808080
+
+
+def mma_ks(size_q):
+    """K-steps of four source towers (bconv_mma_table)"""
+    ks = (size_q + 3) // 4
+    return (ks + 1) & ~1 if ks > 8 else ks
+
+
+def mma_tpc(size_q, size_p, lds_max=64 * 1024, red_bytes=64, src_bytes=32):
+    """(tiles, target tiles per chunk): the most tiles whose fragments [tpc][ks][64 lanes][16 B],
+    reduction rows [4 tpc] and source rows [4 ks] fit the LDS budget (bconv_mma_lds)"""
+    ks, tiles = mma_ks(size_q), (size_p + 3) // 4
+    lds = lambda tpc: tpc * (ks * 1024 + 4 * red_bytes) + 4 * ks * src_bytes  # noqa: E731
+    tpc = 0
+    while tpc < tiles and lds(tpc + 1) <= lds_max:
+        tpc += 1
+    return tiles, tpc
+
+
+def mma_spq(p):
+    """the host's predicate for the special-prime reduction: every target 2^L - d, 33 <= L <= 60,
+    0 < d < 2^32 and (2^(81-L) + 1) d + 2^49 + 2 d < 2^L"""
+    for pj in p:
+        L = int(pj).bit_length()
+        d = (1 << L) - int(pj) if 33 <= L <= 60 else 0
+        if not (0 < d < 1 << 32 and ((1 << (81 - L)) + 1) * d + (1 << 49) + 2 * d < 1 << L):
+            return False
+    return True
+
+
+def extreme_columns(q):
+    """Three columns given by their y_i = [x_i (Q/q_i)^-1]_{q_i}: q_i - 1 in every tower (nu = size_q +
+    0.5, alpha = size_q: the last row of alphaQModp), and the values whose signed base-256 digits are
+    the largest (127 in every position) and the most negative (-128, -127, ...) a tower allows, the
+    bounds of the matrix-core kernel's partial sums.  -> [3][len(q)] residues x_i"""
+    Q = BT.product(q)
+    ys = [[int(m) - 1 for m in q], [min(int(m) - 1, DIGITS_MAX) for m in q], [DIGITS_MIN % int(m) for m in q]]
+    return [[y * (Q // int(m) % int(m)) % int(m) for y, m in zip(row, q)] for row in ys]
+
+
+def plant_extremes(x, kinds, q):
+    """overwrite the last three coefficients of every batch entry (uniform ones) with extreme_columns"""
+    n = x.shape[2]
+    assert (kinds[:, n - 3:] == UNIFORM).all()
+    x[:, :, n - 3:] = np.array(extreme_columns(q), dtype=np.uint64).T
+    kinds[:, n - 3:] = EXTREME
+    return x, kinds
+
+
+def switch_case_mma(O, log_n, sq, sp):
+    """(q, p, x [SWITCH_BATCH][sq][n], kinds) of one SWITCH_CASES_MMA entry, built once: switch_inputs'
+    planted coefficients plus the extreme columns"""
+    key = ("mma", log_n, sq, sp)
+    if key not in _switch_cases:
+        if (log_n, sq, sp) in SWITCH_MMA_MIXED:
+            from test_mixed_moduli_oracle import mixed_chain
+
+            m, _ = mixed_chain(log_n, [MIXED_BITS[i % len(MIXED_BITS)] for i in range(sq + sp)], generic=True)
+        else:
+            m, _ = O.moduli_chain(log_n, sq + sp)
+        q, p = m[:sq], m[sq:]
+        x, kinds = switch_inputs(q, 1 << log_n, SWITCH_BATCH, 2000 + 31 * sq + sp)
+        _switch_cases[key] = (q, p) + plant_extremes(x, kinds, q)
+    return _switch_cases[key]
+
+
+def switch_case_cap(O):
+    """(q, p, x [SWITCH_CAP_BATCH][sq][n], kinds) of SWITCH_CAP_CASE: batch entries 0 and 3 (the first
+    and the second trip of the matrix-core kernel's group loop) start with 4096 coefficients of
+    switch_inputs, the rest is uniform; every entry ends with the extreme columns"""
+    log_n, sq, sp = SWITCH_CAP_CASE
+    key = ("cap", log_n, sq, sp)
+    if key not in _switch_cases:
+        n = 1 << log_n
+        m, _ = O.moduli_chain(log_n, sq + sp)
+        q, p = m[:sq], m[sq:]
+        rng = np.random.default_rng(3000)
+        x = np.stack([np.stack([rng.integers(0, int(qi), size=n, dtype=np.uint64) for qi in q])
+                      for _ in range(SWITCH_CAP_BATCH)])
+        kinds = np.full((SWITCH_CAP_BATCH, n), UNIFORM)
+        for b in (0, SWITCH_CAP_BATCH - 1):
+            xs, ks = switch_inputs(q, 4096, 1, 3001 + b)
+            x[b, :, :4096], kinds[b, :4096] = xs[0], ks[0]
+        _switch_cases[key] = (q, p) + plant_extremes(x, kinds, q)
     return _switch_cases[key]
 
 

@@ -88,6 +88,139 @@ def test_planted_inputs_tell_fused_from_separate_rounding(O, log_n, sq, sp):
     assert len(hot) >= 1 and hot[0] == 0
 
 
+def _hot_planted(x, kinds, q):
+    """indices (flat, batch-major) of the planted coefficients on which a fused sum gives another alpha"""
+    sel = np.flatnonzero(kinds.reshape(-1) == R.PLANTED)
+    ys = R.switch_ys(x, q)
+    ref = R.nu_switch(ys, q).astype(np.int64).reshape(-1)
+    hot = []
+    for c in sel:
+        yc = [int(y.reshape(-1)[c]) for y in ys]
+        assert int(R.nu_switch_scalar(yc, q)) == ref[c]
+        if int(R.nu_switch_fused(yc, q)) != ref[c]:
+            hot.append(c)
+    return sel, hot
+
+
+def _extremes_reach_the_last_alpha(x, kinds, q, p):
+    """the three extreme columns of every batch entry: y_i = q_i - 1 gives alpha = size_q (the last row
+    of alphaQModp, which alpha_of's clamp guards), and the digit columns hold the y_i they claim"""
+    n = x.shape[2]
+    assert (kinds[:, n - 3:] == R.EXTREME).all() and (kinds[:, :n - 3] != R.EXTREME).all()
+    _, alpha = R.switch_crt_basis(x, q, p, want_alpha=True)
+    assert (alpha[:, n - 3] == len(q)).all()
+    if len(q) >= 12:  # with many sources nothing else gets there
+        assert alpha[kinds != R.EXTREME].max() < len(q)
+    ys = R.switch_ys(x, q)
+    for i, m in enumerate(q):
+        assert (ys[i][:, n - 3] == m - 1).all()
+        assert (ys[i][:, n - 2] == min(m - 1, R.DIGITS_MAX)).all() and (ys[i][:, n - 1] == R.DIGITS_MIN % m).all()
+
+
+@pytest.mark.parametrize("log_n,sq,sp", R.SWITCH_CASES_MMA)
+def test_mma_cases_planted_and_extreme_inputs(O, log_n, sq, sp):
+    """bfv_ref.SWITCH_CASES_MMA as test_planted_inputs_tell_fused_from_separate_rounding has it for
+    SWITCH_CASES: at 12 .. 64 sources a fused chain still gives another alpha on planted coefficients
+    (coefficient 0 among them), in batch entry 0 alone too; plus the extreme columns."""
+    q, p, x, kinds = R.switch_case_mma(O, log_n, sq, sp)
+    sel, hot = _hot_planted(x, kinds, q)
+    print(f"({log_n}, {sq}, {sp}): fused alpha differs on {len(hot)} of {len(sel)} planted coefficients")
+    assert len(sel) == x.shape[0] * x.shape[2] // 4
+    assert len(hot) >= 1 and hot[0] == 0
+    _extremes_reach_the_last_alpha(x, kinds, q, p)
+
+
+def test_mma_case_table():
+    """The K-step count, the target chunks and the reduction variant of every SWITCH_CASES_MMA entry,
+    from the host's arithmetic restated in bfv_ref (bconv_mma_table / bconv_mma_lds: 1 KiB of
+    fragments per tile and K-step, a 64-byte row per target, a 32-byte row per source, 64 KiB)."""
+    assert [R.mma_ks(sq) for _, sq, _ in R.SWITCH_CASES_MMA] == [3, 6, 7, 8, 10, 12, 14, 16]
+    reached = {R.mma_ks(sq) for _, sq, _ in R.SWITCH_CASES + R.SWITCH_CASES_MMA if sq <= 64}
+    assert reached == set(range(1, 9)) | {10, 12, 14, 16}  # every instantiation of k_switch_mma
+    chunks = {}
+    for log_n, sq, sp in R.SWITCH_CASES_MMA:
+        assert log_n >= 5  # the matrix-core kernel needs a wave of 32 coefficients
+        tiles, tpc = R.mma_tpc(sq, sp)
+        chunks[(log_n, sq, sp)] = -(-tiles // tpc)
+    assert R.mma_tpc(32, 28) == (7, 7) and R.mma_tpc(32, 29) == (8, 7)  # KS 8: a second chunk from 29 targets
+    assert R.mma_tpc(64, 12) == (3, 3) and R.mma_tpc(64, 13) == (4, 3)  # KS 16: from 13 targets
+    assert [c for c, v in chunks.items() if v >= 2] == [(6, 32, 29), (6, 64, 13)]
+    assert all(R.mma_ks(sq) == ks for (_, sq, _), ks in R.SWITCH_MMA_MIXED.items())
+    assert sorted(R.SWITCH_MMA_MIXED.values()) == [6, 12]  # no special-prime reduction below and above KS 8
+
+
+@pytest.mark.parametrize("log_n,sq,sp", R.SWITCH_CASES_MMA)
+def test_mma_case_reduction_variant(O, log_n, sq, sp):
+    """mm_spq of each chain: the 60-bit chain's targets are 2^60 - d (special-prime reduction), the
+    mixed generic chain's are not; the mixed chain holds a tower below 32 bits and one of 60"""
+    q, p, _, _ = R.switch_case_mma(O, log_n, sq, sp)
+    mixed = (log_n, sq, sp) in R.SWITCH_MMA_MIXED
+    assert R.mma_spq(p) == (not mixed)
+    if mixed:
+        bits = {m.bit_length() for m in q + p}
+        assert min(bits) < 32 and max(bits) == 60
+    assert len(set(q + p)) == sq + sp
+
+
+def test_switch_cap_case(O):
+    """SWITCH_CAP_CASE has more blocks than the matrix-core kernel's grid cap, a partial second trip
+    of the group loop whose coefficients (batch entry 3) carry sensitive planted values too."""
+    blocks_per_cu, cus = 3, 256  # BCONV_MMA_BLOCKS_PER_CU (csrc/bconv_mma.hpp) and the grid cap's CU count
+    log_n, sq, sp = R.SWITCH_CAP_CASE
+    q, p, x, kinds = R.switch_case_cap(O)
+    tiles, tpc = R.mma_tpc(sq, sp)
+    chunks = -(-tiles // tpc)
+    cap = cus * blocks_per_cu // chunks
+    blocks = R.SWITCH_CAP_BATCH * (1 << log_n) // 256  # 8 waves of 32 coefficients each
+    assert cap < blocks < 2 * cap and (cap, blocks) == (768, 1024)
+    assert R.mma_ks(sq) == 1 and R.mma_spq(p)
+    sel, hot = _hot_planted(x, kinds, q)
+    first_of_second_trip = cap * 256
+    assert hot[0] == 0 and any(c >= first_of_second_trip for c in hot)
+    _extremes_reach_the_last_alpha(x, kinds, q, p)
+
+
+@pytest.mark.parametrize("log_n,sq,sp", R.SWITCH_CASES + R.SWITCH_CASES_MMA)
+def test_fast_switch_is_the_exact_one(O, log_n, sq, sp):
+    """bfv_ref's 64-bit-word path (fast = True) gives the residues of the Python-integer path on the
+    planted, special and extreme inputs of every GPU switch case, 22-bit to 60-bit towers"""
+    mma = (log_n, sq, sp) in R.SWITCH_CASES_MMA
+    q, p, x, _ = (R.switch_case_mma if mma else R.switch_case)(O, log_n, sq, sp)
+    x = x[:, :, :256]
+    assert np.array_equal(R.switch_crt_basis(x, q, p, fast=True), R.switch_crt_basis(x, q, p))
+
+
+def test_fast_word_products():
+    """mulmod_const against Python integers on boundary words and moduli of 22 to 62 bits"""
+    rng = np.random.default_rng(5)
+    for m in (4194301, (1 << 31) - 1, (1 << 32) + 15, (1 << 60) - 93, (1 << 62) + 135, (1 << 63) - 25):
+        a = np.concatenate([np.array([0, 1, m - 1, m, 2 * m - 1, (1 << 64) - 1, 1 << 63, (1 << 32) - 1, 1 << 32],
+                                     dtype=np.uint64), rng.integers(0, 1 << 64, size=500, dtype=np.uint64)])
+        for c in (0, 1, m - 1, m // 2, int(rng.integers(0, m))):
+            assert R.mulmod_const(a, c, m).tolist() == [int(v) * c % m for v in a]
+
+
+@pytest.mark.parametrize("tech,sq,sr", [(BT.HPS, 2, 3), (BT.HPSPOVERQ, 2, 2), (BT.HPS, 5, 5)])
+def test_fast_eval_mult_is_the_exact_one(O, tech, sq, sr):
+    """EvalMult and ExpandCRTBasis (ScaleAndRound and both switches inside) by the two paths, on a
+    60-bit and on a mixed 22-60-bit chain"""
+    from test_mixed_moduli_oracle import mixed_chain
+
+    log_n, n = 6, 64
+    for m, rt in (O.moduli_chain(log_n, sq + sr), mixed_chain(log_n, R.MIXED_BITS[:sq + sr], generic=True)):
+        q, rq, r, rr = m[:sq], rt[:sq], m[sq:], rt[sq:]
+        T = BT.BfvTables(q, r, T_PLAIN, tech)
+        ring = R.Ring(O, log_n, q, rq, r, rr)
+        cts = [O.uniform_dcrt(2, sq, n, q, 60 + k) for k in range(4)]
+        for c in cts:
+            c[:, :, :3] = np.array([[0, 1, v - 1] for v in q], dtype=np.uint64)
+        for a, b in zip(R.eval_mult(O, T, ring, *cts, fast=True), R.eval_mult(O, T, ring, *cts)):
+            assert np.array_equal(a, b)
+        for ev in (False, True):
+            assert np.array_equal(R.expand_crt_basis(O, cts[0], q, r, ring.tb_q, ring.tb_r, ev, fast=True),
+                                  R.expand_crt_basis(O, cts[0], q, r, ring.tb_q, ring.tb_r, ev))
+
+
 SR_CASES = [(2, 60), (4, 60), (16, 60), (4, 40), (3, 30)]
 
 

@@ -4,7 +4,9 @@ limb and 128-bit kernels), ExpandCRTBasis, ScaleAndRound (both alpha branches)
 and EvalMult for HPS and HPSPOVERQ.  The switch inputs carry the planted
 near-Q/2 coefficients on which a fused or reordered double sum gives another
 alpha (tests/test_bfv_oracle.py asserts that property on these very inputs,
-bfv_ref.SWITCH_CASES)."""
+bfv_ref.SWITCH_CASES and SWITCH_CASES_MMA; the latter reach every K-step count
+of the matrix-core kernel, a second target chunk and, with SWITCH_CAP_CASE, the
+grid cap)."""
 import numpy as np
 import pytest
 from conftest import load_golden
@@ -86,6 +88,58 @@ def test_switch_crt_basis(hip, log_n, sq, sp, batch):
         assert np.array_equal(got, want), f"kernel {kernel}: {np.count_nonzero(got != want)} words differ"
         assert np.array_equal(host(dx), x)
         bc.close()
+
+
+def switch_case_mma(log_n, sq, sp):
+    """the same for one R.SWITCH_CASES_MMA entry"""
+    q, p, x, _ = R.switch_case_mma(O, log_n, sq, sp)
+    key = ("mma", log_n, sq, sp)
+    if key not in _switch_want:
+        _switch_want[key] = R.switch_crt_basis(x, q, p)
+    return q, p, x, _switch_want[key]
+
+
+def _switch_kernels(H, sq):
+    return [H.BCONV_KERNEL_AUTO, H.BCONV_KERNEL_WIDE] + ([H.BCONV_KERNEL_LIMB] if sq <= 16 else [])
+
+
+def _check_switch(H, ctx, log_n, q, p, x, want, kernel):
+    batch = x.shape[0]
+    bc = converter(H, ctx, log_n, q, p, kernel)
+    dx, out = dev(x), out_buf(batch, len(p), 1 << log_n)
+    bc.switch_exact(dx.data_ptr(), out.data_ptr(), batch, stream())
+    got = host(out)
+    bad = np.argwhere(got != want)
+    assert not len(bad), f"kernel {kernel}: {len(bad)} words differ, first (batch, target, coefficient) {bad[0]}"
+    assert np.array_equal(host(dx), x)
+    bc.close()
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+@pytest.mark.parametrize("log_n,sq,sp", R.SWITCH_CASES_MMA)
+def test_switch_crt_basis_mma_steps(hip, log_n, sq, sp, batch):
+    """Every K-step count of k_switch_mma that R.SWITCH_CASES leaves out (3, 6, 7, 8 and the WIDE
+    combine's 10, 12, 14, 16), with and without the special-prime reduction, two cases with a second
+    target chunk; the inputs hold the planted near-Q/2 coefficients, alpha = size_q and the extreme
+    digit columns (tests/test_bfv_oracle.py).  The other kernels run on the same inputs."""
+    H, ctx = hip
+    q, p, x, want = switch_case_mma(log_n, sq, sp)
+    for kernel in _switch_kernels(H, sq):
+        _check_switch(H, ctx, log_n, q, p, x[:batch], want[:batch], kernel)
+
+
+def test_switch_crt_basis_past_the_grid_cap(hip):
+    """1024 blocks of 256 coefficients against the matrix-core kernel's grid cap of 768: the group
+    loop's second, partial trip (batch entry 3, which holds planted coefficients of its own)."""
+    H, ctx = hip
+    blocks_per_cu = 3  # BCONV_MMA_BLOCKS_PER_CU (csrc/bconv_mma.hpp); the cap is 256 CUs x this / chunks
+    log_n, sq, sp = R.SWITCH_CAP_CASE
+    tiles, tpc = R.mma_tpc(sq, sp)
+    assert R.SWITCH_CAP_BATCH * (1 << log_n) // 256 > 256 * blocks_per_cu // -(-tiles // tpc)
+    q, p, x, _ = R.switch_case_cap(O)
+    want = R.switch_crt_basis(x, q, p)
+    for kernel in (H.BCONV_KERNEL_AUTO, H.BCONV_KERNEL_LIMB, H.BCONV_KERNEL_WIDE):
+        _check_switch(H, ctx, log_n, q, p, x, want, kernel)
 
 
 @pytest.mark.parametrize("batch", [1, 3])

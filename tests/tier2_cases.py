@@ -144,6 +144,12 @@ def _draw(kind, seed, attempt):
         c["data_seed"] = int(rng.integers(0, 1 << 31))
         return c
     assert kind == "keyswitch"
+    return keyswitch_draw(rng, seed, pin, kind)
+
+
+def keyswitch_draw(rng, seed, pin, kind="keyswitch"):
+    """The HYBRID key-switch draw from rng (None: dnum cannot be distributed, draw again); shared with
+    tests/tier3_cases.py, whose rotation cases are this draw plus their own parameters."""
     log_n = _log_n(rng, seed, 4, pin)
     big = log_n >= 15
     size_q = pin.get("size_q", int(rng.integers(1, 7 if big else 13)))
