@@ -7,7 +7,8 @@ machine code with the allocation raised to 64 or 72 VGPRs is exact
 failure").  csrc/arith.hpp's OFHE_VGPR_FLOOR() holds every kernel at >= 64.
 This test reads the allocation each kernel's descriptor asks the hardware for
 (COMPUTE_PGM_RSRC1.GRANULATED_WORKITEM_VGPR_COUNT, granule 8 on gfx950) from
-the gfx950 code object inside the built library -- no GPU needed.
+every gfx950 code object inside the built library (one offload bundle per
+translation unit) -- no GPU needed.
 """
 import os
 import struct
@@ -37,45 +38,73 @@ def _section_bytes(elf, name):
     return elf[s["off"]:s["off"] + s["size"]]
 
 
-def _gfx950_code_object(lib):
+_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def _gfx950_code_objects(lib):
+    """every gfx950 code object of every offload bundle (one bundle per translation unit)"""
     fb = _section_bytes(lib, ".hip_fatbin")
-    assert fb[:24] == b"__CLANG_OFFLOAD_BUNDLE__"
-    n, = struct.unpack_from("<Q", fb, 24)
-    p = 32
-    for _ in range(n):
-        off, size, tl = struct.unpack_from("<QQQ", fb, p)
-        p += 24
-        triple = fb[p:p + tl].decode()
-        p += tl
-        if triple.endswith("gfx950"):
-            return fb[off:off + size]
-    raise AssertionError("no gfx950 code object in the library")
+    assert fb[:24] == _MAGIC
+    cos = []
+    base = fb.find(_MAGIC)
+    while base >= 0:
+        n, = struct.unpack_from("<Q", fb, base + 24)
+        p = end = base + 32
+        for _ in range(n):
+            off, size, tl = struct.unpack_from("<QQQ", fb, p)
+            p += 24
+            triple = fb[p:p + tl].decode()
+            p += tl
+            end = max(end, p, base + off + size)
+            if triple.endswith("gfx950") and size:
+                cos.append(fb[base + off:base + off + size])
+        base = fb.find(_MAGIC, end)  # the next bundle starts after this one's last entry
+    assert cos, "no gfx950 code object in the library"
+    return cos
 
 
-def kernel_vgpr_allocations(co):
-    """{kernel symbol: VGPRs allocated per lane} from the kernel descriptors"""
+def code_object_kernels(co):
+    """{kernel symbol: (VGPRs allocated per lane, function symbol size)} of one code object"""
     secs = _sections(co)
     symtab = next(s for s in secs if s["type"] == 2)  # SHT_SYMTAB
     strtab = secs[symtab["link"]]
-    out = {}
+    syms = {}
     for k in range(symtab["size"] // symtab["entsize"]):
         name, info, other, shndx, value, size = struct.unpack_from("<IBBHQQ", co, symtab["off"] + k * symtab["entsize"])
         end = co.index(b"\0", strtab["off"] + name)
-        sym = co[strtab["off"] + name:end].decode()
+        syms[co[strtab["off"] + name:end].decode()] = (shndx, value, size)
+    out = {}
+    for sym, (shndx, value, _) in syms.items():
         if not sym.endswith(".kd"):
             continue
         sec = secs[shndx]
         kd = co[sec["off"] + value - sec["addr"]:][:64]
         rsrc1, = struct.unpack_from("<I", kd, 48)
-        out[sym[:-3]] = ((rsrc1 & 0x3F) + 1) * 8
+        out[sym[:-3]] = (((rsrc1 & 0x3F) + 1) * 8, syms[sym[:-3]][2])
     return out
+
+
+def library_kernels(path=LIB):
+    """{kernel symbol: (VGPRs, function size)} over all gfx950 code objects of
+    the library, and the number of kernels in each code object"""
+    merged, counts = {}, []
+    for co in _gfx950_code_objects(open(path, "rb").read()):
+        kernels = code_object_kernels(co)
+        for k, v in kernels.items():
+            # a template launched from two translation units is compiled in both, to the same code
+            assert merged.setdefault(k, v) == v, f"{k} differs between code objects: {merged[k]} vs {v}"
+        counts.append(len(kernels))
+    return merged, counts
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built")
 def test_every_kernel_allocates_at_least_64_vgprs():
-    lib = open(LIB, "rb").read()
-    alloc = kernel_vgpr_allocations(_gfx950_code_object(lib))
+    kernels, counts = library_kernels()
+    alloc = {k: v[0] for k, v in kernels.items()}
     assert len(alloc) > 50, "kernel descriptors not found"
     assert any("k_tensor2" in k for k in alloc) and any("k_eltwise" in k for k in alloc)
+    # every translation unit with kernels is read, not only the first bundle
+    assert any("k_ks_inner" in k for k in alloc), f"keyswitch.hip's kernels not read ({counts})"
+    assert any("k_scale_round" in k for k in alloc), f"bfv_kernels.hpp's kernels not read ({counts})"
     low = {k: v for k, v in alloc.items() if v < 64}
     assert not low, f"kernels below the 64-VGPR floor: {low}"

@@ -129,13 +129,10 @@ int ofhe_hip_scale_round_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
     }
     ofhe_scale_round_s* r = new (std::nothrow) ofhe_scale_round_s();
     if (!r) return fail(OFHE_ERR_NOMEM, "scale-and-round allocation failed");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(&r->d_mem, h.size() * sizeof(u64));
-    if (e == hipSuccess) e = upload_blocking(r->d_mem, h.data(), h.size() * sizeof(u64));
-    if (e != hipSuccess) {
-        (void)hipFree(r->d_mem);
+    const int rc = alloc_upload(&r->d_mem, h.data(), h.size() * sizeof(u64), "scale-and-round upload", ctx->device);
+    if (rc != OFHE_OK) {
         delete r;
-        return fail(OFHE_ERR_HIP, std::string("scale-and-round upload: ") + hipGetErrorString(e));
+        return rc;
     }
     r->ctx = ctx;
     r->size_q = size_q;

@@ -1,6 +1,8 @@
 // internal.hpp -- definitions shared by the translation units of the backend
 // (ofhe_hip.hip: context, plans, NTT, element-wise ops, base conversion;
-// keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching).
+// keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching, rescaling;
+// bfv.hip: BFV multiplication, ScaleAndRound; comm.hip: multi-device
+// collectives).
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 #include <set>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ofhe_hip.h"
@@ -34,6 +37,36 @@ int post_launch();
         int rc_ = (call);      \
         if (rc_) return rc_;   \
     } while (0)
+
+// Run-time value -> kernel template argument: f is a generic lambda, called
+// with std::true_type / std::false_type, or with std::integral_constant<int, V>
+// for the V of the list that equals v (returns false, calling nothing, when
+// none does).  Read the constant as decltype(arg)::value; `if constexpr` on it
+// keeps a combination uninstantiated.
+template <class F>
+inline void with_bool(bool v, F&& f) {
+    if (v)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+template <int... Vs, class F>
+inline bool with_int(int v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// Grid of the streaming kernels, per_block items a block: one thread per item,
+// grid-stride only past the cap (2^22 blocks = 2^30 threads, never reached by a
+// launch of the sizes used).  A full grid keeps more bytes in flight than a
+// capped grid-stride launch (DESIGN.md "Element-wise bandwidth").
+#ifndef OFHE_ELT_GRID
+#define OFHE_ELT_GRID (1u << 22)
+#endif
+inline u32 grid_for(u64 items, u32 per_block = 256) {
+    u64 b = (items + per_block - 1) / per_block;
+    if (b > OFHE_ELT_GRID) b = OFHE_ELT_GRID;
+    return (u32)(b ? b : 1);
+}
 
 // host-side number theory for table construction (setup, not timed)
 inline u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
@@ -124,12 +157,50 @@ inline hipError_t upload_blocking(void* dst, const void* src, size_t bytes) {
     return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
 }
 
+// A device table for the setup paths: allocated, filled with upload_blocking,
+// freed again on failure (*d is then left as it was); on `device` if given,
+// else on the current one.
+template <class T>
+inline int alloc_upload(T** d, const void* src, size_t bytes, const char* what, int device = -1) {
+    void* m = nullptr;
+    hipError_t e = device >= 0 ? hipSetDevice(device) : hipSuccess;
+    if (e == hipSuccess) e = hipMalloc(&m, bytes ? bytes : 8);
+    if (e == hipSuccess && bytes) e = upload_blocking(m, src, bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(m);
+        return fail(OFHE_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    *d = static_cast<T*>(m);
+    return OFHE_OK;
+}
+
+// Upload-once tables of one owner (a plan, a converter, a key-switch level):
+// the first call with a key builds the host table (build() returns a vector)
+// and uploads it into freshly allocated memory that no launch has read yet,
+// and the copy has landed before the call returns (upload_blocking), so the
+// caller's kernels, on whatever stream, read complete tables; later calls only
+// look the pointer up and never synchronise.  mu is the owner's lock, held
+// across the upload; the owner frees the map's tables when it is destroyed.
+template <class Key, class T, class Build>
+inline int cached_table(std::mutex& mu, std::map<Key, T*>& tabs, const Key& key, const char* what, const T** out,
+                        Build&& build) {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = tabs.find(key);
+    if (it == tabs.end()) {
+        const auto& h = build();
+        T* d = nullptr;
+        RCCHK(alloc_upload(&d, h.data(), h.size() * sizeof(h[0]), what));
+        it = tabs.emplace(key, d).first;
+    }
+    *out = it->second;
+    return OFHE_OK;
+}
+
 // ApproxSwitchCRTBasis launch (strides and output gap from A)
 int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);
 
 // SwitchCRTBasis (exact, bfv_kernels.hpp) launch with b's tables; strides and
-// output gap from A (a copy of b->args with the caller's strides).  The
-// alphaQModp / qInv tables are built and uploaded on b's first exact call.
+// output gap from A (a copy of b->args with the caller's strides).
 int switch_exact_run(ofhe_bconv_t b, const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);
 
 }  // namespace ofhe
@@ -210,8 +281,7 @@ struct ofhe_plan_s {
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     std::mutex fork_mu;  // guards st / ev_* (plan_tune, the two-stream pipeline)
     // rescaling scalar tables (keyswitch.hip: DropLastElementAndScale /
-    // ModReduce), uploaded once per distinct content into memory no launch
-    // has read yet, kept until destroy
+    // ModReduce), one per distinct content (cached_table), kept until destroy
     std::mutex tab_mu;
     std::map<std::vector<ofhe::u64>, ofhe::u64*> tabs;
 };
@@ -220,18 +290,14 @@ struct ofhe_bconv_s {
     ofhe_ctx_t ctx = nullptr;
     ofhe::BconvArgs args{};
     ofhe::u64* d_mem = nullptr;
-    // ofhe_hip_approx_mod_down's constant tables (P^-1 mod q_i, and for t > 0
-    // t^-1 mod p_j, t mod q_i), uploaded once per distinct (t, P^-1 mod q)
-    // into memory no launch has read yet and kept until destroy, so steady-state
-    // calls upload nothing and never synchronise
+    // cached_table: ofhe_hip_approx_mod_down's constant tables (P^-1 mod q_i,
+    // and for t > 0 t^-1 mod p_j, t mod q_i) under the key (P^-1 mod q, t), and
+    // the exact switch's tables under the empty key; kept until destroy
     std::mutex tab_mu;
     std::map<std::vector<ofhe::u64>, ofhe::u64*> tabs;
     // k_bconv_cols in ofhe_hip_approx_mod_up / _down (options.separate_cols = 0)
     bool bcols = true;
-    // ofhe_hip_switch_crt_basis: host copies of the moduli, and the exact
-    // switch's tables (qInv, alphaQModp) derived from them on the first exact
-    // call (under tab_mu), uploaded once and kept until destroy
+    // ofhe_hip_switch_crt_basis: host copies of the moduli; the exact switch's
+    // tables (qInv, alphaQModp) are derived from them on the first exact call
     std::vector<ofhe::u64> hq, hp;
-    void* d_exact = nullptr;
-    ofhe::ExactArgs exact{};
 };

@@ -31,7 +31,7 @@ using namespace ofhe;
 #define OFHE_KS_MERGE 1
 #endif
 // KeySwitchCore's two ModDowns as one set of launches over 2 x batch
-// (mod_down_run2) instead of two forked streams (OFHE_KS_MD2)
+// (mod_down_run, nout = 2) instead of two forked streams (OFHE_KS_MD2)
 #ifndef OFHE_KS_MD2
 #define OFHE_KS_MD2 1
 #endif
@@ -50,15 +50,6 @@ u64 prod_mod(const u64* ms, u32 n, u32 skip, u64 m) {
     for (u32 k = 0; k < n; k++)
         if (k != skip) r = mulmod(r, ms[k] % m, m);
     return r;
-}
-
-// one thread per item for the streaming kernels (grid-stride only past 2^30
-// threads): a full grid keeps more bytes in flight than a capped grid-stride
-// launch (ofhe_hip.hip eltwise, DESIGN.md "Element-wise bandwidth")
-u32 grid_for(u64 items) {
-    u64 b = (items + 255) / 256;
-    if (b > (1u << 22)) b = 1u << 22;
-    return (u32)(b ? b : 1);
 }
 
 TowerScalar scalar_of(u64 q, u64 s) {
@@ -101,100 +92,59 @@ static bool md_icol(const ModDownArgs& A) {
     return A.bcols && A.icol && !A.t_q && !A.tinv_p && A.plan_p == A.plan_q && A.plan_q->log_n == 17;
 }
 
-int mod_down_run(const ModDownArgs& A, const u64* x, u64 xstride, u64* out, u64 ostride, u32 batch, hipStream_t s) {
+// ApproxModDown of nout = 1 or 2 inputs of `batch` entries each into out[k];
+// input k starts at x + k * batch * xstride (KeySwitchCore's ct1 follows its
+// ct0), so the P-part INTT, the base conversion and the column pass run once
+// over nout * batch polynomials; only the last pass, which writes the caller's
+// out[k], runs per output.
+int mod_down_run(const ModDownArgs& A, const u64* x, u64 xstride, u64* const* out, u32 nout, u64 ostride, u32 batch,
+                 hipStream_t s) {
     const u32 log_n = A.plan_q->log_n;
     const u64 N = 1ull << log_n;
+    const u32 bn = nout * batch;
     Scratch sp, sq;
-    RCCHK(sp.alloc((size_t)batch * A.size_p * N * 8, s, A.plan_q->ctx));
-    RCCHK(sq.alloc((size_t)batch * A.size_q * N * 8, s, A.plan_q->ctx));
+    RCCHK(sp.alloc((size_t)bn * A.size_p * N * 8, s, A.plan_q->ctx));
+    RCCHK(sq.alloc((size_t)bn * A.size_q * N * 8, s, A.plan_q->ctx));
     const u64 ps = A.size_p * N, qs = A.size_q * N;
-    if (md_icol(A)) {
-        BconvArgs B = A.bconv;
-        B.in_stride = ps;
-        B.out_stride = qs;
-        B.gap_at = A.size_q;
-        B.gap = 0;
-        B.lazy_out = 1;
-        if (bconv_cols_ok(A.plan_q, B)) {
-            // partP's INTT: its block pass here, its column pass inside the conversion
-            RCCHK(plan_ntt_inv_block(A.plan_p, A.p0, A.size_p, x + qs, xstride, sp.w(), ps, batch, s));
-            RCCHK(bconv_cols_run(A.plan_q, A.q0, B, sp.w(), sq.w(), batch, s, (int)A.p0));
-            return plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x, xstride, out, ostride,
-                                    reinterpret_cast<const u64*>(A.pinv), batch, s, 2);
-        }
-    }
-    // partP: P towers to coefficient form (dcrtpoly-impl.h:1147-1153)
-    RCCHK(plan_ntt_range(A.plan_p, true, A.p0, A.size_p, x + qs, sp.w(), xstride, ps, batch, s));
-    if (A.tinv_p) RCCHK(scale_towers(A.tinv_p, sp.w(), sp.w(), ps, ps, batch, A.size_p, log_n, s));
-    // partPSwitchedToQ (1156-1157)
     BconvArgs B = A.bconv;
     B.in_stride = ps;
     B.out_stride = qs;
     B.gap_at = A.size_q;
     B.gap = 0;
     B.lazy_out = 1;  // a forward NTT (after an optional tower scale) follows
+    // partP: P towers to coefficient form (dcrtpoly-impl.h:1147-1153)
+    const bool icol = md_icol(A) && bconv_cols_ok(A.plan_q, B);
+    if (icol)  // only the INTT's block pass here, its column pass inside the conversion
+        RCCHK(plan_ntt_inv_block(A.plan_p, A.p0, A.size_p, x + qs, xstride, sp.w(), ps, bn, s));
+    else
+        RCCHK(plan_ntt_range(A.plan_p, true, A.p0, A.size_p, x + qs, sp.w(), xstride, ps, bn, s));
+    if (A.tinv_p) RCCHK(scale_towers(A.tinv_p, sp.w(), sp.w(), ps, ps, bn, A.size_p, log_n, s));
+    // partPSwitchedToQ (1156-1157), then SetFormat(EVALUATION) and
+    // ans_i = (x_i - switched_i) * PInvModq_i (1165-1173): for log_n >= 12 one
+    // transform whose block pass applies the subtraction and the scalar while
+    // the values are in registers
+    const u64* pinv = reinterpret_cast<const u64*>(A.pinv);
+    const bool block_tail = log_n >= 12;
     if (A.bcols && !A.t_q && bconv_cols_ok(A.plan_q, B)) {
         // the conversion writes the Q towers' column-pass output (k_bconv_cols)
-        RCCHK(bconv_cols_run(A.plan_q, A.q0, B, sp.w(), sq.w(), batch, s));
-        return plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x, xstride, out, ostride,
-                                reinterpret_cast<const u64*>(A.pinv), batch, s, 2);
+        RCCHK(bconv_cols_run(A.plan_q, A.q0, B, sp.w(), sq.w(), bn, s, icol ? (int)A.p0 : -1));
+    } else {
+        RCCHK(bconv_run(B, sp.w(), sq.w(), bn, s));
+        if (A.t_q) RCCHK(scale_towers(A.t_q, sq.w(), sq.w(), qs, qs, bn, A.size_q, log_n, s));
+        if (block_tail)
+            RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x, xstride, out[0], ostride, pinv, bn, s, 1));
+        else
+            RCCHK(plan_ntt_range(A.plan_q, false, A.q0, A.size_q, sq.w(), sq.w(), qs, qs, bn, s));
     }
-    RCCHK(bconv_run(B, sp.w(), sq.w(), batch, s));
-    if (A.t_q) RCCHK(scale_towers(A.t_q, sq.w(), sq.w(), qs, qs, batch, A.size_q, log_n, s));
-    // SetFormat(EVALUATION), then ans_i = (x_i - switched_i) * PInvModq_i
-    // (1165-1173): one transform whose block pass applies the subtraction and
-    // the scalar while the values are in registers
-    if (log_n >= 12)
-        return plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x, xstride, out, ostride,
-                                reinterpret_cast<const u64*>(A.pinv), batch, s);
-    RCCHK(plan_ntt_range(A.plan_q, false, A.q0, A.size_q, sq.w(), sq.w(), qs, qs, batch, s));
-    return sub_scale(A.pinv, x, sq.w(), out, xstride, qs, ostride, batch, A.size_q, log_n, s);
-}
-
-// The two ApproxModDowns of KeySwitchCore in one set of launches: ct1
-// follows ct0 in memory (x1 = x0 + batch * xstride), so the P-part INTT, the
-// base conversion and the column pass run once over 2 * batch polynomials;
-// only the block pass, which writes the caller's out0 / out1, runs twice.
-int mod_down_run2(const ModDownArgs& A, const u64* x0, u64 xstride, u64* out0, u64* out1, u64 ostride, u32 batch,
-                  hipStream_t s) {
-    const u32 log_n = A.plan_q->log_n;
-    const u64 N = 1ull << log_n;
-    const u32 b2 = 2 * batch;
-    Scratch sp, sq;
-    RCCHK(sp.alloc((size_t)b2 * A.size_p * N * 8, s, A.plan_q->ctx));
-    RCCHK(sq.alloc((size_t)b2 * A.size_q * N * 8, s, A.plan_q->ctx));
-    const u64 ps = A.size_p * N, qs = A.size_q * N;
-    BconvArgs B = A.bconv;
-    B.in_stride = ps;
-    B.out_stride = qs;
-    B.gap_at = A.size_q;
-    B.gap = 0;
-    B.lazy_out = 1;  // a forward NTT (after an optional tower scale) follows
-    const bool icol = md_icol(A) && bconv_cols_ok(A.plan_q, B);
-    if (icol)  // partP's INTT: its block pass here, its column pass inside the conversion
-        RCCHK(plan_ntt_inv_block(A.plan_p, A.p0, A.size_p, x0 + qs, xstride, sp.w(), ps, b2, s));
-    else
-        RCCHK(plan_ntt_range(A.plan_p, true, A.p0, A.size_p, x0 + qs, sp.w(), xstride, ps, b2, s));
-    if (A.tinv_p) RCCHK(scale_towers(A.tinv_p, sp.w(), sp.w(), ps, ps, b2, A.size_p, log_n, s));
-    const u64* x1 = x0 + (u64)batch * xstride;
-    u64* sq1 = sq.w() + (u64)batch * qs;
-    const u64* pinv = reinterpret_cast<const u64*>(A.pinv);
-    if (A.bcols && !A.t_q && bconv_cols_ok(A.plan_q, B)) {
-        // the conversion writes the Q towers' column-pass output directly
-        RCCHK(bconv_cols_run(A.plan_q, A.q0, B, sp.w(), sq.w(), b2, s, icol ? (int)A.p0 : -1));
-        RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x0, xstride, out0, ostride, pinv, batch, s, 2));
-        return plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq1, qs, x1, xstride, out1, ostride, pinv, batch, s, 2);
+    for (u32 k = 0; k < nout; k++) {
+        const u64* xk = x + (u64)k * batch * xstride;
+        u64* sqk = sq.w() + (u64)k * batch * qs;
+        if (block_tail)
+            RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sqk, qs, xk, xstride, out[k], ostride, pinv, batch, s, 2));
+        else
+            RCCHK(sub_scale(A.pinv, xk, sqk, out[k], xstride, qs, ostride, batch, A.size_q, log_n, s));
     }
-    RCCHK(bconv_run(B, sp.w(), sq.w(), b2, s));
-    if (A.t_q) RCCHK(scale_towers(A.t_q, sq.w(), sq.w(), qs, qs, b2, A.size_q, log_n, s));
-    if (log_n >= 12) {
-        RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x0, xstride, out0, ostride, pinv, b2, s, 1));
-        RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq.w(), qs, x0, xstride, out0, ostride, pinv, batch, s, 2));
-        return plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sq1, qs, x1, xstride, out1, ostride, pinv, batch, s, 2);
-    }
-    RCCHK(plan_ntt_range(A.plan_q, false, A.q0, A.size_q, sq.w(), sq.w(), qs, qs, b2, s));
-    RCCHK(sub_scale(A.pinv, x0, sq.w(), out0, xstride, qs, ostride, batch, A.size_q, log_n, s));
-    return sub_scale(A.pinv, x1, sq1, out1, xstride, qs, ostride, batch, A.size_q, log_n, s);
+    return OFHE_OK;
 }
 
 }  // namespace
@@ -248,41 +198,23 @@ int ofhe_hip_approx_mod_down(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, co
     HIPCHK(hipSetDevice(pq->ctx->device));
     hipStream_t s = pick(stream);
     const u32 Q = pq->towers, P = pp->towers;
-    // Tables cached per (t, P^-1 mod q) in the converter: the first call with
-    // a key uploads into freshly allocated memory that no launch has read yet
-    // and waits for the copy to land (upload_blocking), so the kernels below,
-    // on whatever stream, read complete tables; later calls only look the
-    // table up and never synchronise.
+    // tables cached per (P^-1 mod q, t) in the converter
     std::vector<u64> key(p_inv_modq, p_inv_modq + Q);
     key.push_back(t);
-    u64* dtab = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(bc->tab_mu);
-        auto it = bc->tabs.find(key);
-        if (it != bc->tabs.end()) {
-            dtab = it->second;
-        } else {
-            std::vector<TowerScalar> tab(Q + (t ? P + Q : 0));
-            for (u32 i = 0; i < Q; i++) tab[i] = scalar_of(pq->q[i], p_inv_modq[i]);
-            if (t) {
-                for (u32 j = 0; j < P; j++) tab[Q + j] = scalar_of(pp->q[j], invmod(t % pp->q[j], pp->q[j]));  // tInvModp
-                for (u32 i = 0; i < Q; i++) tab[Q + P + i] = scalar_of(pq->q[i], t);  // t mod q_i
-            }
-            const size_t words = tab.size() * 3;
-            HIPCHK(hipMalloc(&dtab, words * sizeof(u64)));
-            hipError_t e = upload_blocking(dtab, tab.data(), words * sizeof(u64));
-            if (e != hipSuccess) {
-                (void)hipFree(dtab);
-                return fail(OFHE_ERR_HIP, std::string("mod-down tables: ") + hipGetErrorString(e));
-            }
-            bc->tabs.emplace(std::move(key), dtab);
+    const u64* dtab = nullptr;
+    RCCHK(cached_table(bc->tab_mu, bc->tabs, key, "mod-down tables", &dtab, [&] {
+        std::vector<TowerScalar> tab(Q + (t ? P + Q : 0));
+        for (u32 i = 0; i < Q; i++) tab[i] = scalar_of(pq->q[i], p_inv_modq[i]);
+        if (t) {
+            for (u32 j = 0; j < P; j++) tab[Q + j] = scalar_of(pp->q[j], invmod(t % pp->q[j], pp->q[j]));  // tInvModp
+            for (u32 i = 0; i < Q; i++) tab[Q + P + i] = scalar_of(pq->q[i], t);  // t mod q_i
         }
-    }
+        return tab;
+    }));
     const TowerScalar* d = (const TowerScalar*)dtab;
     ModDownArgs A{pq, pp, 0, 0, Q, P, bc->args, d, t ? d + Q : nullptr, t ? d + Q + P : nullptr, bc->bcols};
     const u64 N = 1ull << pq->log_n;
-    RCCHK(mod_down_run(A, x, (u64)(Q + P) * N, out, (u64)Q * N, batch, s));
-    return OFHE_OK;
+    return mod_down_run(A, x, (u64)(Q + P) * N, &out, 1, (u64)Q * N, batch, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -473,16 +405,12 @@ static int level_get(ofhe_ks_t k, u32 size_ql, KsLevel** out) {
             pinv[i] = scalar_of(k->q[i], invmod(pm, k->q[i]));
             pmodq[i] = scalar_of(k->q[i], pm);
         }
-        hipError_t e = hipSetDevice(k->ctx->device);
-        if (e == hipSuccess) e = hipMalloc(&L->d_tow, sizeof(KsTower) * tow.size());
-        if (e == hipSuccess) e = hipMalloc(&L->d_pinv, sizeof(TowerScalar) * pinv.size());
-        if (e == hipSuccess) e = hipMalloc(&L->d_pmodq, sizeof(TowerScalar) * pmodq.size());
-        if (e == hipSuccess) e = upload_blocking(L->d_tow, tow.data(), sizeof(KsTower) * tow.size());
-        if (e == hipSuccess)
-            e = upload_blocking(L->d_pinv, pinv.data(), sizeof(TowerScalar) * pinv.size());
-        if (e == hipSuccess)
-            e = upload_blocking(L->d_pmodq, pmodq.data(), sizeof(TowerScalar) * pmodq.size());
-        if (e != hipSuccess) rc = fail(OFHE_ERR_HIP, std::string("level upload: ") + hipGetErrorString(e));
+        const int dev = k->ctx->device;
+        rc = alloc_upload(&L->d_tow, tow.data(), sizeof(KsTower) * tow.size(), "level upload", dev);
+        if (rc == OFHE_OK)
+            rc = alloc_upload(&L->d_pinv, pinv.data(), sizeof(TowerScalar) * pinv.size(), "level upload", dev);
+        if (rc == OFHE_OK)
+            rc = alloc_upload(&L->d_pmodq, pmodq.data(), sizeof(TowerScalar) * pmodq.size(), "level upload", dev);
     }
     if (rc != OFHE_OK) {
         level_free(L);
@@ -494,25 +422,22 @@ static int level_get(ofhe_ks_t k, u32 size_ql, KsLevel** out) {
 }
 
 static int level_t_tables(ofhe_ks_t k, KsLevel* L, u64 t, const TowerScalar** out) {
-    std::lock_guard<std::mutex> lk(k->mu);
-    auto it = L->tscale.find(t);
-    if (it != L->tscale.end()) {
-        *out = it->second;
-        return OFHE_OK;
-    }
-    const u32 P = k->size_p, l = L->size_ql;
-    std::vector<TowerScalar> tab(P + l);
-    for (u32 j = 0; j < P; j++) tab[j] = scalar_of(k->p[j], invmod(t % k->p[j], k->p[j]));
-    for (u32 i = 0; i < l; i++) tab[P + i] = scalar_of(k->q[i], t);
-    TowerScalar* d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(TowerScalar) * tab.size()));
-    hipError_t e = upload_blocking(d, tab.data(), sizeof(TowerScalar) * tab.size());
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(OFHE_ERR_HIP, std::string("t tables: ") + hipGetErrorString(e));
-    }
-    L->tscale[t] = d;
-    *out = d;
+    return cached_table(k->mu, L->tscale, t, "t tables", out, [&] {
+        const u32 P = k->size_p, l = L->size_ql;
+        std::vector<TowerScalar> tab(P + l);
+        for (u32 j = 0; j < P; j++) tab[j] = scalar_of(k->p[j], invmod(t % k->p[j], k->p[j]));
+        for (u32 i = 0; i < l; i++) tab[P + i] = scalar_of(k->q[i], t);
+        return tab;
+    });
+}
+
+// The key-switch engine's ApproxModDown (P -> the level's Q towers) with
+// plaintext modulus t (0: none)
+static int ks_md_args(ofhe_ks_t k, KsLevel* L, u64 t, ModDownArgs* A) {
+    const TowerScalar* tt = nullptr;
+    if (t) RCCHK(level_t_tables(k, L, t, &tt));
+    *A = ModDownArgs{k->plan, k->plan, 0, k->size_q, L->size_ql, k->size_p, L->down->args, L->d_pinv,
+                     tt, tt ? tt + k->size_p : nullptr, k->bcols, k->icol};
     return OFHE_OK;
 }
 
@@ -648,16 +573,11 @@ static int ks_fast_core_ext_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, cons
             own.cnt[j] = L->cnt[j];
         }
         const u64 c_stride = (u64)size_ql << k->log_n;
-#define OFHE_KS_BS(B_)                                                                                      \
-    hipLaunchKernelGGL((k_ks_inner_bs<B_, OFHE_KS_CPT>), g, blk, 0, s, L->d_tow, digits, key_b, key_a, ct0, ct1, \
-                       key_stride, batch, rows, k->log_n, towers, c, c_stride, own)
-        switch (L->beta) {
-            case 1: OFHE_KS_BS(1); break;
-            case 2: OFHE_KS_BS(2); break;
-            case 3: OFHE_KS_BS(3); break;
-            default: OFHE_KS_BS(4); break;
-        }
-#undef OFHE_KS_BS
+        // beta is in [1, 4] here (ofhe_hip_ks_digits); anything else took the beta = 4 kernel before too
+        with_int<1, 2, 3, 4>(L->beta ? (int)L->beta : 4, [&](auto B_) {
+            hipLaunchKernelGGL((k_ks_inner_bs<decltype(B_)::value, OFHE_KS_CPT>), g, blk, 0, s, L->d_tow, digits, key_b,
+                               key_a, ct0, ct1, key_stride, batch, rows, k->log_n, towers, c, c_stride, own);
+        });
     } else {
         if (c) return fail(OFHE_ERR_STATE, "internal: own-tower reads need beta <= 4");
         const u64 npairs = ((u64)batch * towers << k->log_n) / 2;
@@ -677,13 +597,10 @@ int ofhe_hip_ks_fast_core_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
 }
 
 static int ks_mod_down_impl(ofhe_ks_t k, KsLevel* L, const u64* x, u64* out, u64 t, u32 batch, hipStream_t s) {
-    const TowerScalar* tt = nullptr;
-    if (t) RCCHK(level_t_tables(k, L, t, &tt));
-    const u32 l = L->size_ql, P = k->size_p;
-    ModDownArgs A{k->plan, k->plan, 0, k->size_q, l, P, L->down->args, L->d_pinv,
-                  tt ? tt : nullptr, tt ? tt + P : nullptr, k->bcols, k->icol};
-    const u64 N = 1ull << k->log_n;
-    return mod_down_run(A, x, (u64)(l + P) * N, out, (u64)l * N, batch, s);
+    ModDownArgs A;
+    RCCHK(ks_md_args(k, L, t, &A));
+    const u64 N = 1ull << k->log_n, l = L->size_ql;
+    return mod_down_run(A, x, (l + k->size_p) * N, &out, 1, l * N, batch, s);
 }
 
 int ofhe_hip_ks_mod_down(ofhe_ks_t k, uint32_t size_ql, const uint64_t* x, uint64_t* out, uint64_t t, uint32_t batch,
@@ -715,12 +632,10 @@ int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uin
     RCCHK(ks_fast_core_ext_impl(k, L, size_ql, dg.w(), key_b, key_a, c0, c1, batch, s, own_from_c ? c : nullptr));
     if (OFHE_KS_MD2) {
         // both ModDowns in one set of launches (c1 = c0 + batch * poly)
-        const TowerScalar* tt = nullptr;
-        if (t) RCCHK(level_t_tables(k, L, t, &tt));
-        const u32 l = L->size_ql, P = k->size_p;
-        ModDownArgs A{k->plan, k->plan, 0, k->size_q, l, P, L->down->args, L->d_pinv,
-                      tt ? tt : nullptr, tt ? tt + P : nullptr, k->bcols, k->icol};
-        return mod_down_run2(A, c0, poly, out0, out1, (u64)l * N, batch, s);
+        ModDownArgs A;
+        RCCHK(ks_md_args(k, L, t, &A));
+        u64* const outs[2] = {out0, out1};
+        return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s);
     }
     KsFork fk;  // after dg, ct: joins before they are freed
     RCCHK(fk.open(k, s));
@@ -771,19 +686,13 @@ static int ks_inner_rot(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* digits,
     const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
     const u64 nthreads = (u64)batch * towers << k->log_n;
     const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
-#define OFHE_KS_ROT(B_)                                                                                        \
-    hipLaunchKernelGGL((k_ks_inner_rot<B_>), g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R, nrot, out0, out1, \
-                       key_stride, rot_stride, nthreads, k->log_n, towers, size_ql)
-    switch (L->beta) {
-        case 1: OFHE_KS_ROT(1); break;
-        case 2: OFHE_KS_ROT(2); break;
-        case 3: OFHE_KS_ROT(3); break;
-        case 4: OFHE_KS_ROT(4); break;
-        default:
-            hipLaunchKernelGGL(k_ks_inner_rot_wide, g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R, nrot, out0,
-                               out1, key_stride, rot_stride, nthreads, L->beta, k->log_n, towers, size_ql);
-    }
-#undef OFHE_KS_ROT
+    const bool narrow = with_int<1, 2, 3, 4>((int)L->beta, [&](auto B_) {
+        hipLaunchKernelGGL((k_ks_inner_rot<decltype(B_)::value>), g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R,
+                           nrot, out0, out1, key_stride, rot_stride, nthreads, k->log_n, towers, size_ql);
+    });
+    if (!narrow)
+        hipLaunchKernelGGL(k_ks_inner_rot_wide, g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R, nrot, out0, out1,
+                           key_stride, rot_stride, nthreads, L->beta, k->log_n, towers, size_ql);
     return post_launch();
 }
 
@@ -813,12 +722,10 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
     KsLevel* L = nullptr;
     RCCHK(level_get(k, size_ql, &L));
     hipStream_t s = pick(stream);
-    const TowerScalar* tt = nullptr;
-    if (t) RCCHK(level_t_tables(k, L, t, &tt));
+    ModDownArgs A;
+    RCCHK(ks_md_args(k, L, t, &A));
     const u32 l = L->size_ql, P = k->size_p;
     const u64 N = 1ull << k->log_n, poly = (u64)(l + P) * N, per_rot = (u64)batch * l * N;
-    ModDownArgs A{k->plan, k->plan, 0, k->size_q, l, P, L->down->args, L->d_pinv,
-                  tt ? tt : nullptr, tt ? tt + P : nullptr, k->bcols, k->icol};
     u32 one[KS_ROT_CAP];
     for (auto& v : one) v = 1;
     // the order of the reference: ModDown, += c0, then the automorphism
@@ -834,7 +741,8 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
         u64* md1 = md.w() + (u64)nr * per_rot;
         RCCHK(ks_inner_rot(k, L, size_ql, digits, nullptr, nr, one, key_b + r0, key_a + r0, ct.w(), ct1,
                            (u64)batch * poly, batch, s));
-        RCCHK(mod_down_run2(A, ct.w(), poly, md.w(), md1, (u64)l * N, nr * batch, s));
+        u64* const mds[2] = {md.w(), md1};
+        RCCHK(mod_down_run(A, ct.w(), poly, mds, 2, (u64)l * N, nr * batch, s));
         KsRotIdx I{};
         for (u32 r = 0; r < nr; r++) I.kinv[r] = kinv[r0 + r];
         hipLaunchKernelGGL(k_add_automorphism, dim3(grid_for(per_rot), nr), dim3(256), 0, s, L->d_tow, md.w(), md1,
@@ -866,12 +774,10 @@ int ofhe_hip_automorphism(ofhe_plan_t p, uint32_t k, int eval_form, const uint64
     if (k % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
     HIPCHK(hipSetDevice(p->ctx->device));
     const u64 total = (u64)batch * p->towers << p->log_n;
-    if (eval_form)
-        hipLaunchKernelGGL(k_automorphism<true>, dim3(grid_for(total)), dim3(256), 0, pick(stream), p->d_tc, src, dst,
-                           k, total, p->log_n, p->towers);
-    else
-        hipLaunchKernelGGL(k_automorphism<false>, dim3(grid_for(total)), dim3(256), 0, pick(stream), p->d_tc, src,
-                           dst, k, total, p->log_n, p->towers);
+    with_bool(eval_form != 0, [&](auto ev) {
+        hipLaunchKernelGGL(k_automorphism<decltype(ev)::value>, dim3(grid_for(total)), dim3(256), 0, pick(stream),
+                           p->d_tc, src, dst, k, total, p->log_n, p->towers);
+    });
     return post_launch();
 }
 
@@ -888,23 +794,10 @@ int ofhe_hip_automorphism(ofhe_plan_t p, uint32_t k, int eval_form, const uint64
 #ifndef OFHE_RESCALE_FUSE
 #define OFHE_RESCALE_FUSE 1  // 0: k_switch_scale then the column pass (A/B)
 #endif
+// a scalar table of the plan, keyed by its own content
 static int plan_table(ofhe_plan_t p, const std::vector<u64>& words, const u64** out) {
-    std::lock_guard<std::mutex> lk(p->tab_mu);
-    auto it = p->tabs.find(words);
-    if (it != p->tabs.end()) {
-        *out = it->second;
-        return OFHE_OK;
-    }
-    u64* d = nullptr;
-    HIPCHK(hipMalloc(&d, words.size() * sizeof(u64)));
-    hipError_t e = upload_blocking(d, words.data(), words.size() * sizeof(u64));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(OFHE_ERR_HIP, std::string("rescale tables: ") + hipGetErrorString(e));
-    }
-    p->tabs.emplace(words, d);
-    *out = d;
-    return OFHE_OK;
+    return cached_table(p->tab_mu, p->tabs, words, "rescale tables", out,
+                        [&]() -> const std::vector<u64>& { return words; });
 }
 
 static int rescale_check(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, const u64* out, u64 os, u32 batch) {
@@ -958,10 +851,9 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
         A.xstride = xs;
         A.y = out;
         A.ystride = os;
-        if (mode == SW_AXPY)
-            hipLaunchKernelGGL(k_switch_scale<SW_AXPY>, dim3((u32)blocks), dim3(256), 0, s, A, bpr);
-        else
-            hipLaunchKernelGGL(k_switch_scale<SW_XPYA>, dim3((u32)blocks), dim3(256), 0, s, A, bpr);
+        with_int<SW_AXPY, SW_XPYA>(mode, [&](auto m) {
+            hipLaunchKernelGGL(k_switch_scale<decltype(m)::value>, dim3((u32)blocks), dim3(256), 0, s, A, bpr);
+        });
         RCCHK(post_launch());
         // DropLastElementAndScale switches the coefficient-form towers to
         // evaluation form (dcrtpoly-impl.h:765-766); ModReduce does not

@@ -410,25 +410,24 @@ int ofhe_hip_plan_create_ex(ofhe_ctx_t ctx, uint32_t log_n, uint32_t towers, con
     if (opt.generic_moduli) p->spq = false;
     p->split = split;
     p->opts = opt;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tc, sizeof(TowerConst) * towers);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = hipMalloc(&p->d_itw, sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tw3, sizeof(u64) * (tw3.size() ? tw3.size() : 2));
-    if (e == hipSuccess && tw3.size())
-        e = upload_blocking(p->d_tw3, tw3.data(), sizeof(u64) * tw3.size());
-    if (e == hipSuccess) e = hipMalloc(&p->d_dtw, sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = hipMalloc(&p->d_twist, sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = hipMalloc(&p->d_twist_r, sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = upload_blocking(p->d_dtw, dtw.data(), sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = upload_blocking(p->d_twist, twist.data(), sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = upload_blocking(p->d_twist_r, twist_r.data(), sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = upload_blocking(p->d_tc, tc.data(), sizeof(TowerConst) * towers);
-    if (e == hipSuccess) e = upload_blocking(p->d_tw, tw.data(), sizeof(u64) * 2 * TN);
-    if (e == hipSuccess) e = upload_blocking(p->d_itw, itw.data(), sizeof(u64) * 2 * TN);
-    if (e != hipSuccess) {
+    const auto words = [](const std::vector<u64>& v) { return sizeof(u64) * v.size(); };
+    const struct {
+        void** dst;
+        const void* src;
+        size_t bytes;
+    } tables[] = {{(void**)&p->d_tc, tc.data(), sizeof(TowerConst) * towers},
+                  {(void**)&p->d_tw, tw.data(), words(tw)},
+                  {(void**)&p->d_itw, itw.data(), words(itw)},
+                  {(void**)&p->d_tw3, tw3.data(), words(tw3)},  // empty below N = 4096
+                  {(void**)&p->d_dtw, dtw.data(), words(dtw)},
+                  {(void**)&p->d_twist, twist.data(), words(twist)},
+                  {(void**)&p->d_twist_r, twist_r.data(), words(twist_r)}};
+    int rc = OFHE_OK;
+    for (const auto& t : tables)
+        if (rc == OFHE_OK) rc = alloc_upload(t.dst, t.src, t.bytes, "plan upload", ctx->device);
+    if (rc != OFHE_OK) {
         ofhe_hip_plan_destroy(p);
-        return fail(OFHE_ERR_HIP, std::string("plan upload: ") + hipGetErrorString(e));
+        return rc;
     }
     *plan = p;
     return OFHE_OK;
@@ -545,47 +544,42 @@ static int check_common(ofhe_plan_t p, uint32_t batch) {
 #define OFHE_COLS_CPT 2
 #endif
 // Every launcher picks the special-prime instantiation when the plan allows it.
-template <int KA, bool INV, bool SPQ>
-static void launch_cols_t(const PlanArgs& a, const u64* src, u64* dst, u32 batch, hipStream_t s) {
-    // two columns per thread (16-byte accesses) while registers allow
-    constexpr int CPT = KA <= 4 ? OFHE_COLS_CPT : 1;
-    const u32 nwg = batch * a.towers * (16 / CPT);
-    hipLaunchKernelGGL((k_cols<KA, INV, CPT, SPQ>), dim3(nwg), dim3(256), 0, s, a, src, dst, batch, nwg,
-                       SwSrc{nullptr, 0, 0, nullptr, 1, 0});
-}
-template <int KA, bool SPQ>
-static void launch_cols_sw(const PlanArgs& a, const SwSrc& S, u64* dst, u32 batch, hipStream_t s) {
-    constexpr int CPT = KA <= 4 ? OFHE_COLS_CPT : 1;
-    const u32 nwg = batch * a.towers * (16 / CPT);
-    hipLaunchKernelGGL((k_cols<KA, false, CPT, SPQ, true>), dim3(nwg), dim3(256), 0, s, a, (const u64*)nullptr, dst,
-                       batch, nwg, S);
-}
-
-template <bool SPQ>
-static void launch_cols_s(const PlanArgs& a, bool inv, const u64* src, u64* dst, u32 batch, hipStream_t s) {
-    switch (a.log_n - 12) {
-#define CASE(K)                                                 \
-    case K:                                                     \
-        if (inv)                                                \
-            launch_cols_t<K, true, SPQ>(a, src, dst, batch, s); \
-        else                                                    \
-            launch_cols_t<K, false, SPQ>(a, src, dst, batch, s);\
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5)
-#undef CASE
-        default: break;
-    }
-}
-static void launch_cols(const PlanArgs& a, bool spq, bool inv, const u64* src, u64* dst, u32 batch, hipStream_t s) {
-    if (spq)
-        launch_cols_s<true>(a, inv, src, dst, batch, s);
-    else
-        launch_cols_s<false>(a, inv, src, dst, batch, s);
-}
-
-// column pass for log_n > 12: k_tcols / k_tcols9 (8 / 9 stages) unless SPLIT_COLS, else k_cols
+//
+// Column pass for log_n > 12, the only launch site of its kernels: k_tcols
+// (8 stages: SPLIT_T8, SPLIT_T8B9), k_tcols9 (9: SPLIT_T9) or k_cols
+// (log_n - 12: SPLIT_COLS).  lift (forward only, not SPLIT_T9; src unused):
+// the SWS variants, whose loads lift the towers from *lift (plan_cols_switch).
 static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, const u64* src, u64* dst, u32 batch,
-                           hipStream_t s);
+                           hipStream_t s, const SwSrc* lift = nullptr) {
+    const SwSrc S = lift ? *lift : SwSrc{nullptr, 0, 0, nullptr, 1, 0};
+    const u32 polys = batch * a.towers;
+    with_bool(spq, [&](auto sp) { with_bool(inv, [&](auto iv) { with_bool(lift != nullptr, [&](auto sw) {
+        constexpr bool SP = decltype(sp)::value, INV = decltype(iv)::value, SWS = decltype(sw)::value;
+        if constexpr (!(INV && SWS)) {
+            if (split == SPLIT_T9) {
+                if constexpr (!SWS) {
+                    const u32 nwg = polys * 16;  // 16-column tiles of 512 rows
+                    hipLaunchKernelGGL((k_tcols9<INV, SP>), dim3(nwg), dim3(512), 0, s, a, src, dst, batch, nwg);
+                }
+            } else if (split != SPLIT_COLS) {
+                with_int<16, 17>(split == SPLIT_T8B9 ? 17 : 16, [&](auto ln) {
+                    constexpr int LOGN = decltype(ln)::value;
+                    const u32 nwg = polys * ((1u << (LOGN - 8)) / TCOLS_W);  // 256 or 512 columns
+                    hipLaunchKernelGGL((k_tcols<INV, SP, SWS, LOGN>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a, src,
+                                       dst, batch, nwg, S);
+                });
+            } else {
+                with_int<1, 2, 3, 4, 5>((int)a.log_n - 12, [&](auto ka) {
+                    // two columns per thread (16-byte accesses) while registers allow
+                    constexpr int KA = decltype(ka)::value, CPT = KA <= 4 ? OFHE_COLS_CPT : 1;
+                    const u32 nwg = polys * (16 / CPT);
+                    hipLaunchKernelGGL((k_cols<KA, INV, CPT, SP, SWS>), dim3(nwg), dim3(256), 0, s, a, src, dst,
+                                       batch, nwg, S);
+                });
+            }
+        }
+    }); }); });
+}
 
 // Pass split for log_n > 12 (the plan's split, internal.hpp): the block pass
 // runs the last 8 (SPLIT_T8 / T9: k_block NR = 2), 9 (SPLIT_T8B9: NR = 3
@@ -594,54 +588,11 @@ template <int MODE>
 static void launch_block(const PlanArgs& a, bool spq, const u64* src, u64* dst, const u64* b, u32 batch,
                          hipStream_t s, int split = SPLIT_COLS) {
     const u32 nwg = batch * a.towers * (1u << (a.log_n - 12));
-#define LB(SP, NR, SK) \
-    hipLaunchKernelGGL((k_block<MODE, SP, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b, batch, nwg)
-    if (split == SPLIT_T8 || split == SPLIT_T9) {
-        if (spq) LB(true, 2, 0); else LB(false, 2, 0);
-    } else if (split == SPLIT_T8B9) {
-        if (spq) LB(true, 3, 3); else LB(false, 3, 3);
-    } else {
-        if (spq) LB(true, 3, 0); else LB(false, 3, 0);
-    }
-#undef LB
-}
-
-static void launch_tcols(const PlanArgs& a, bool spq, int split, bool inv, const u64* src, u64* dst, u32 batch,
-                         hipStream_t s) {
-    if (split == SPLIT_T8B9) {
-        const u32 nwg = batch * a.towers * (512 / TCOLS_W);
-#define LT17(I, SP)                                                                                           \
-    hipLaunchKernelGGL((k_tcols<I, SP, false, 17>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a, src, dst, batch, nwg, \
-                       SwSrc{nullptr, 0, 0, nullptr, 1, 0})
-        if (inv) {
-            if (spq) LT17(true, true); else LT17(true, false);
-        } else {
-            if (spq) LT17(false, true); else LT17(false, false);
-        }
-#undef LT17
-        return;
-    }
-    if (split == SPLIT_T9) {
-        const u32 nwg = batch * a.towers * 16;  // 16-column tiles of 512 rows
-#define LT9(I, SP) hipLaunchKernelGGL((k_tcols9<I, SP>), dim3(nwg), dim3(512), 0, s, a, src, dst, batch, nwg)
-        if (inv) {
-            if (spq) LT9(true, true); else LT9(true, false);
-        } else {
-            if (spq) LT9(false, true); else LT9(false, false);
-        }
-#undef LT9
-        return;
-    }
-    const u32 nwg = batch * a.towers * (256 / TCOLS_W);
-#define LT(I, SP)                                                                                 \
-    hipLaunchKernelGGL((k_tcols<I, SP>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a, src, dst, batch, nwg, \
-                       SwSrc{nullptr, 0, 0, nullptr, 1, 0})
-    if (inv) {
-        if (spq) LT(true, true); else LT(true, false);
-    } else {
-        if (spq) LT(false, true); else LT(false, false);
-    }
-#undef LT
+    with_bool(spq, [&](auto sp) { with_int<8, 9, 12>((int)block_stages(split, a.log_n), [&](auto st) {
+        constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
+        hipLaunchKernelGGL((k_block<MODE, decltype(sp)::value, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b,
+                           batch, nwg);
+    }); });
 }
 
 template <int MODE>
@@ -649,18 +600,10 @@ static void launch_small(const PlanArgs& a, bool spq, const u64* src, u64* dst, 
                          hipStream_t s) {
     const u32 N = 1u << a.log_n;
     const u32 thr = N / 2 >= 256 ? 256 : (N / 2 < 64 ? 64 : N / 2);
-    if (spq)
-        hipLaunchKernelGGL((k_small<MODE, true>), dim3(batch * a.towers), dim3(thr), 0, s, a, src, dst, b, batch);
-    else
-        hipLaunchKernelGGL((k_small<MODE, false>), dim3(batch * a.towers), dim3(thr), 0, s, a, src, dst, b, batch);
-}
-
-static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, const u64* src, u64* dst, u32 batch,
-                           hipStream_t s) {
-    if (split != SPLIT_COLS)
-        launch_tcols(a, spq, split, inv, src, dst, batch, s);
-    else
-        launch_cols(a, spq, inv, src, dst, batch, s);
+    with_bool(spq, [&](auto sp) {
+        hipLaunchKernelGGL((k_small<MODE, decltype(sp)::value>), dim3(batch * a.towers), dim3(thr), 0, s, a, src, dst,
+                           b, batch);
+    });
 }
 
 
@@ -710,38 +653,7 @@ int plan_cols_switch(ofhe_plan_t p, u32 t0, u32 count, const u64* last, u64 lstr
     a.sstride = a.dstride = ystride;
     pre %= ql;
     const SwSrc S{last, lstride, ql, tab, pre, pre == 1 ? 0 : shoup_pre(pre, ql)};
-    if (p->split == SPLIT_T8) {  // N = 2^16: k_tcols
-        const u32 nwg = batch * a.towers * (256 / TCOLS_W);
-        if (p->spq)
-            hipLaunchKernelGGL((k_tcols<false, true, true>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
-                               (const u64*)nullptr, y, batch, nwg, S);
-        else
-            hipLaunchKernelGGL((k_tcols<false, false, true>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
-                               (const u64*)nullptr, y, batch, nwg, S);
-        return post_launch();
-    }
-    if (p->split == SPLIT_T8B9) {  // N = 2^17: k_tcols, 512 columns
-        const u32 nwg = batch * a.towers * (512 / TCOLS_W);
-        if (p->spq)
-            hipLaunchKernelGGL((k_tcols<false, true, true, 17>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
-                               (const u64*)nullptr, y, batch, nwg, S);
-        else
-            hipLaunchKernelGGL((k_tcols<false, false, true, 17>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
-                               (const u64*)nullptr, y, batch, nwg, S);
-        return post_launch();
-    }
-    switch (p->log_n - 12) {
-#define CASE(K)                                                 \
-    case K:                                                     \
-        if (p->spq)                                             \
-            launch_cols_sw<K, true>(a, S, y, batch, s);         \
-        else                                                    \
-            launch_cols_sw<K, false>(a, S, y, batch, s);        \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5)
-#undef CASE
-        default: break;
-    }
+    launch_colpass(a, p->spq, p->split, false, nullptr, y, batch, s, &S);
     return post_launch();
 }
 
@@ -889,11 +801,6 @@ int ofhe_hip_ntt_mul_intt_stage(ofhe_plan_t p, int stage, const uint64_t* a_, co
     return post_launch();
 }
 
-// grid cap of the streaming element-wise launches (grid-stride beyond it;
-// 2^22 blocks = 2^31 pairs per pass, never reached by a launch of the sizes used)
-#ifndef OFHE_ELT_GRID
-#define OFHE_ELT_GRID (1u << 22)
-#endif
 template <int OP>
 static int eltwise(ofhe_plan_t p, const u64* a, const u64* b, u64* c, u32 batch, void* stream) {
     int rc = check_common(p, batch);
@@ -901,10 +808,8 @@ static int eltwise(ofhe_plan_t p, const u64* a, const u64* b, u64* c, u32 batch,
     if (!a || !b || !c) return fail(OFHE_ERR_ARG, "NULL data pointer");
     HIPCHK(hipSetDevice(p->ctx->device));
     const u64 npairs = (u64)batch * p->towers * ((u64)1 << p->log_n) / 2;
-    u64 blocks = (npairs + 256 * elt_unroll(OP) - 1) / (256 * elt_unroll(OP));
-    if (blocks > OFHE_ELT_GRID) blocks = OFHE_ELT_GRID;
-    hipLaunchKernelGGL((k_eltwise<OP>), dim3((u32)blocks), dim3(256), 0, pick(stream), p->d_tc, a, b,
-                       c, npairs, p->log_n, p->towers);
+    hipLaunchKernelGGL((k_eltwise<OP>), dim3(grid_for(npairs, 256 * elt_unroll(OP))), dim3(256), 0, pick(stream),
+                       p->d_tc, a, b, c, npairs, p->log_n, p->towers);
     return post_launch();
 }
 
@@ -966,10 +871,8 @@ static int scalar_op(ofhe_plan_t p, const u64* a, const u64* s, u64* c, u32 batc
                                p->log_n, cnt, t0, p->towers, idx);
         } else {
             const u64 npairs = ((u64)batch * cnt << p->log_n) / 2;
-            u64 blocks = (npairs + 256 * elt_unroll(OP) - 1) / (256 * elt_unroll(OP));
-            if (blocks > OFHE_ELT_GRID) blocks = OFHE_ELT_GRID;
-            hipLaunchKernelGGL((k_scalar<OP>), dim3((u32)blocks), dim3(256), 0, st, S, a, c, npairs, p->log_n, cnt,
-                               t0, p->towers);
+            hipLaunchKernelGGL((k_scalar<OP>), dim3(grid_for(npairs, 256 * elt_unroll(OP))), dim3(256), 0, st, S, a,
+                               c, npairs, p->log_n, cnt, t0, p->towers);
         }
         RCCHK(post_launch());
     }
@@ -1000,9 +903,7 @@ int ofhe_hip_fill_uniform(ofhe_plan_t p, uint64_t* dst, uint32_t batch, uint32_t
     if (!dst) return fail(OFHE_ERR_ARG, "NULL data pointer");
     HIPCHK(hipSetDevice(p->ctx->device));
     const u64 words = (u64)batch * p->towers << p->log_n;
-    u64 blocks = (words + 255) / 256;
-    if (blocks > (1u << 22)) blocks = 1u << 22;
-    hipLaunchKernelGGL(k_fill_uniform, dim3((u32)blocks), dim3(256), 0, pick(stream), p->d_tc, dst, words,
+    hipLaunchKernelGGL(k_fill_uniform, dim3(grid_for(words)), dim3(256), 0, pick(stream), p->d_tc, dst, words,
                        p->log_n, p->towers, batch_offset, seed);
     return post_launch();
 }
@@ -1156,13 +1057,10 @@ int ofhe_hip_bconv_create_ex(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, ui
     if (!b) return fail(OFHE_ERR_NOMEM, "bconv allocation failed");
     b->ctx = ctx;
     b->bcols = !opt.separate_cols;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(&b->d_mem, words_all * sizeof(u64));
-    if (e == hipSuccess) e = upload_blocking(b->d_mem, h.data(), words_all * sizeof(u64));
-    if (e != hipSuccess) {
-        (void)hipFree(b->d_mem);
+    const int rc = alloc_upload(&b->d_mem, h.data(), words_all * sizeof(u64), "bconv upload", ctx->device);
+    if (rc != OFHE_OK) {
         delete b;
-        return fail(OFHE_ERR_HIP, std::string("bconv upload: ") + hipGetErrorString(e));
+        return rc;
     }
     BconvArgs& A = b->args;
     A.qv = b->d_mem;
@@ -1195,7 +1093,6 @@ int ofhe_hip_bconv_destroy(ofhe_bconv_t b) {
     if (!b) return fail(OFHE_ERR_ARG, "bconv is NULL");
     if (b->ctx) (void)hipSetDevice(b->ctx->device);
     (void)hipFree(b->d_mem);
-    (void)hipFree(b->d_exact);
     for (auto& kv : b->tabs) (void)hipFree(kv.second);
     delete b;
     return OFHE_OK;
@@ -1222,61 +1119,52 @@ int bconv_cols_run(ofhe_plan_t p, u32 t0, const BconvArgs& B, const u64* x, u64*
     const u64 nwg = (u64)batch * (4096 / BC_COLS);
     if (nwg >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
     const PlanArgs a = args_of(p, t0);
-    switch (B.mm_ks) {
-#define BCC1(K, SP, IC) \
-    hipLaunchKernelGGL((k_bconv_cols<K, SP, IC>), dim3((u32)nwg), dim3(BC_THREADS), 0, s, B, a, x, out, batch, (u32)nwg, src_rel)
-#define BCC(K)                                                   \
-    case K:                                                      \
-        if (p->spq) {                                            \
-            if (src_t0 >= 0) BCC1(K, true, true); else BCC1(K, true, false); \
-        } else {                                                 \
-            if (src_t0 >= 0) BCC1(K, false, true); else BCC1(K, false, false); \
-        }                                                        \
-        break;
-        BCC(1) BCC(2) BCC(3) BCC(4)
-#undef BCC
-#undef BCC1
-        default: break;
-    }
+    with_int<1, 2, 3, 4>((int)B.mm_ks, [&](auto K) { with_bool(p->spq, [&](auto sp) { with_bool(src_t0 >= 0, [&](auto ic) {
+        hipLaunchKernelGGL((k_bconv_cols<decltype(K)::value, decltype(sp)::value, decltype(ic)::value>),
+                           dim3((u32)nwg), dim3(BC_THREADS), 0, s, B, a, x, out, batch, (u32)nwg, src_rel);
+    }); }); });
     return post_launch();
+}
+
+// Kernel choice and launch shape shared by the approximate and the exact
+// converter: the matrix cores for <= 64 sources and N >= 32 unless the handle
+// asks for LIMB / WIDE, over the instantiated K-step counts.
+static bool bconv_use_mma(const BconvArgs& A) {
+    return OFHE_BCONV_MMA && A.mm_tab && A.log_n >= 5 && A.kernel != OFHE_BCONV_KERNEL_WIDE &&
+           A.kernel != OFHE_BCONV_KERNEL_LIMB;
+}
+struct MmaShape {
+    dim3 grid;
+    size_t lds;
+};
+static MmaShape bconv_mma_shape(const BconvArgs& A, u64 total) {
+    const u64 groups = total >> 5;
+    const u32 wpb = BCONV_MMA_THREADS / 64;
+    const u32 chunks = (A.mm_tiles + A.mm_tpc - 1) / A.mm_tpc;
+    u64 gx = (groups + wpb - 1) / wpb;
+    u64 cap = 256ull * BCONV_MMA_BLOCKS_PER_CU / chunks;  // about BPC resident blocks per CU in all
+    if (cap < 1) cap = 1;
+    if (gx > cap) gx = cap;
+    return {dim3((u32)gx, chunks), bconv_mma_lds(A.mm_tpc, A.mm_ks)};
+}
+template <class F>
+static bool with_ksteps(u32 ks, F&& f) {
+    return with_int<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16>((int)ks, f);
 }
 
 int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s) {
     const u64 total = (u64)batch << A.log_n;
     const u64 blocks = (total + 255) / 256;
     if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    const bool generic = A.kernel == OFHE_BCONV_KERNEL_WIDE, limb = A.kernel == OFHE_BCONV_KERNEL_LIMB;
-    if (OFHE_BCONV_MMA && A.mm_tab && A.log_n >= 5 && !generic && !limb) {
-        const u64 groups = total >> 5;
-        const u32 wpb = BCONV_MMA_THREADS / 64;
-        const u32 chunks = (A.mm_tiles + A.mm_tpc - 1) / A.mm_tpc;
-        u64 gx = (groups + wpb - 1) / wpb;
-        u64 cap = 256ull * BCONV_MMA_BLOCKS_PER_CU / chunks;  // about BPC resident blocks per CU in all
-        if (cap < 1) cap = 1;
-        if (gx > cap) gx = cap;
-        const size_t lds = bconv_mma_lds(A.mm_tpc, A.mm_ks);
-        const int var = (A.lazy_out ? 1 : 0) | (A.mm_spq ? 2 : 0);
-        const dim3 grid((u32)gx, chunks);
-        switch (A.mm_ks) {
-#define BM_LAUNCH(K, LZ, SP) \
-    hipLaunchKernelGGL((k_bconv_mma<K, LZ, SP>), grid, dim3(BCONV_MMA_THREADS), lds, s, A, x, out, batch)
-#define BM_CASE(K)                                 \
-    case K:                                        \
-        if (var == 0) BM_LAUNCH(K, false, false);  \
-        if (var == 1) BM_LAUNCH(K, true, false);   \
-        if (var == 2) BM_LAUNCH(K, false, true);   \
-        if (var == 3) BM_LAUNCH(K, true, true);    \
-        break;
-            BM_CASE(1) BM_CASE(2) BM_CASE(3) BM_CASE(4) BM_CASE(5) BM_CASE(6) BM_CASE(7) BM_CASE(8)
-            BM_CASE(10) BM_CASE(12) BM_CASE(14) BM_CASE(16)
-#undef BM_CASE
-#undef BM_LAUNCH
-            default:
-                return fail(OFHE_ERR_STATE, "bconv: bad K-step count");
-        }
-        return post_launch();
+    if (bconv_use_mma(A)) {
+        const MmaShape sh = bconv_mma_shape(A, total);
+        const bool ok = with_ksteps(A.mm_ks, [&](auto K) { with_bool(A.lazy_out, [&](auto lz) { with_bool(A.mm_spq, [&](auto sp) {
+            hipLaunchKernelGGL((k_bconv_mma<decltype(K)::value, decltype(lz)::value, decltype(sp)::value>), sh.grid,
+                               dim3(BCONV_MMA_THREADS), sh.lds, s, A, x, out, batch);
+        }); }); });
+        return ok ? post_launch() : fail(OFHE_ERR_STATE, "bconv: bad K-step count");
     }
-    if (A.size_q <= BCONV_LIMB_QMAX && !generic)
+    if (A.size_q <= BCONV_LIMB_QMAX && A.kernel != OFHE_BCONV_KERNEL_WIDE)
         hipLaunchKernelGGL((k_bconv_limb<BCONV_PT>), dim3((u32)blocks), dim3(256), 0, s, A, x, out, batch);
     else
         hipLaunchKernelGGL((k_bconv<8>), dim3((u32)blocks), dim3(256), 0, s, A, x, out, batch);
@@ -1286,73 +1174,46 @@ int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t
 // The exact switch's tables (CryptoParametersBFVRNS::PrecomputeCRTTables):
 // qInv[i] = 1.0 / double(q_i) (bfvrns-cryptoparameters.cpp:270-273, 441-444)
 // and alphaQModp[a][j] = (Q mod p_j) a mod p_j, a = 0 .. size_q (343-350,
-// 418-424), from the handle's moduli; uploaded once into memory no launch has
-// read yet (upload_blocking), so later calls only read the cached pointers.
-static int exact_tables(ofhe_bconv_t b) {
-    std::lock_guard<std::mutex> lk(b->tab_mu);
-    if (b->d_exact) return OFHE_OK;
+// 418-424), from the handle's moduli, cached under the empty key.
+static int exact_tables(ofhe_bconv_t b, ExactArgs* E) {
     const u32 sq = (u32)b->hq.size(), sp = (u32)b->hp.size();
-    std::vector<u64> h(sq + (size_t)(sq + 1) * sp);
-    for (u32 i = 0; i < sq; i++) {
-        const double inv = 1. / static_cast<double>(b->hq[i]);
-        std::memcpy(&h[i], &inv, sizeof(double));
-    }
-    for (u32 j = 0; j < sp; j++) {
-        const u64 pj = b->hp[j];
-        u64 qmod = 1 % pj;
-        for (u32 i = 0; i < sq; i++) qmod = mulmod(qmod, b->hq[i] % pj, pj);
-        for (u32 a = 0; a <= sq; a++) h[sq + (size_t)a * sp + j] = mulmod(qmod, a % pj, pj);
-    }
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, h.size() * sizeof(u64)));
-    hipError_t e = upload_blocking(d, h.data(), h.size() * sizeof(u64));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(OFHE_ERR_HIP, std::string("exact switch tables: ") + hipGetErrorString(e));
-    }
-    b->exact.qinv = reinterpret_cast<const double*>(d);
-    b->exact.aq = reinterpret_cast<const u64*>(d) + sq;
-    b->d_exact = d;
+    const u64* d = nullptr;
+    RCCHK(cached_table(b->tab_mu, b->tabs, std::vector<u64>(), "exact switch tables", &d, [&] {
+        std::vector<u64> h(sq + (size_t)(sq + 1) * sp);
+        for (u32 i = 0; i < sq; i++) {
+            const double inv = 1. / static_cast<double>(b->hq[i]);
+            std::memcpy(&h[i], &inv, sizeof(double));
+        }
+        for (u32 j = 0; j < sp; j++) {
+            const u64 pj = b->hp[j];
+            u64 qmod = 1 % pj;
+            for (u32 i = 0; i < sq; i++) qmod = mulmod(qmod, b->hq[i] % pj, pj);
+            for (u32 a = 0; a <= sq; a++) h[sq + (size_t)a * sp + j] = mulmod(qmod, a % pj, pj);
+        }
+        return h;
+    }));
+    E->qinv = reinterpret_cast<const double*>(d);
+    E->aq = d + sq;
     return OFHE_OK;
 }
 
-// SwitchCRTBasis: one launch.  The kernel choice mirrors bconv_run's (matrix
-// cores for <= 64 sources and N >= 32 unless the handle asks for LIMB / WIDE).
+// SwitchCRTBasis: one launch.
 int switch_exact_run(ofhe_bconv_t b, const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s) {
     if (A.lazy_out) return fail(OFHE_ERR_ARG, "internal: the exact switch has canonical outputs only");
-    RCCHK(exact_tables(b));
-    const ExactArgs E = b->exact;
+    ExactArgs E{};
+    RCCHK(exact_tables(b, &E));
     const u64 total = (u64)batch << A.log_n;
     const u64 blocks = (total + 255) / 256;
     if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    const bool generic = A.kernel == OFHE_BCONV_KERNEL_WIDE, limb = A.kernel == OFHE_BCONV_KERNEL_LIMB;
-    if (OFHE_BCONV_MMA && A.mm_tab && A.log_n >= 5 && !generic && !limb) {
-        const u64 groups = total >> 5;
-        const u32 wpb = BCONV_MMA_THREADS / 64;
-        const u32 chunks = (A.mm_tiles + A.mm_tpc - 1) / A.mm_tpc;
-        u64 gx = (groups + wpb - 1) / wpb;
-        u64 cap = 256ull * BCONV_MMA_BLOCKS_PER_CU / chunks;
-        if (cap < 1) cap = 1;
-        if (gx > cap) gx = cap;
-        const size_t lds = bconv_mma_lds(A.mm_tpc, A.mm_ks);
-        const dim3 grid((u32)gx, chunks);
-        switch (A.mm_ks) {
-#define SX_CASE(K)                                                                                              \
-    case K:                                                                                                     \
-        if (A.mm_spq)                                                                                           \
-            hipLaunchKernelGGL((k_switch_mma<K, true>), grid, dim3(BCONV_MMA_THREADS), lds, s, A, E, x, out, batch);  \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_switch_mma<K, false>), grid, dim3(BCONV_MMA_THREADS), lds, s, A, E, x, out, batch); \
-        break;
-            SX_CASE(1) SX_CASE(2) SX_CASE(3) SX_CASE(4) SX_CASE(5) SX_CASE(6) SX_CASE(7) SX_CASE(8)
-            SX_CASE(10) SX_CASE(12) SX_CASE(14) SX_CASE(16)
-#undef SX_CASE
-            default:
-                return fail(OFHE_ERR_STATE, "bconv: bad K-step count");
-        }
-        return post_launch();
+    if (bconv_use_mma(A)) {
+        const MmaShape sh = bconv_mma_shape(A, total);
+        const bool ok = with_ksteps(A.mm_ks, [&](auto K) { with_bool(A.mm_spq, [&](auto sp) {
+            hipLaunchKernelGGL((k_switch_mma<decltype(K)::value, decltype(sp)::value>), sh.grid,
+                               dim3(BCONV_MMA_THREADS), sh.lds, s, A, E, x, out, batch);
+        }); });
+        return ok ? post_launch() : fail(OFHE_ERR_STATE, "bconv: bad K-step count");
     }
-    if (A.size_q <= BCONV_LIMB_QMAX && !generic)
+    if (A.size_q <= BCONV_LIMB_QMAX && A.kernel != OFHE_BCONV_KERNEL_WIDE)
         hipLaunchKernelGGL((k_switch_limb<BCONV_PT>), dim3((u32)blocks), dim3(256), 0, s, A, E, x, out, batch);
     else
         hipLaunchKernelGGL((k_switch_wide<8>), dim3((u32)blocks), dim3(256), 0, s, A, E, x, out, batch);
