@@ -18,7 +18,10 @@
  *       (mubintvecnat.cpp:111-136, poly-impl.h:312-365),
  *   - the BFV (HPS) multiplication's SwitchCRTBasis / ExpandCRTBasis /
  *     FastExpandCRTBasisPloverQ / ScaleAndRound
- *       (dcrtpoly-impl.h:1178-1230, 1311-1358, 1413-1466, 1876-1955).
+ *       (dcrtpoly-impl.h:1178-1230, 1311-1358, 1413-1466, 1876-1955),
+ *   - the BFV (BEHZ) multiplication's FastBaseConvqToBskMontgomery /
+ *     FastRNSFloorq / FastBaseConvSK
+ *       (dcrtpoly-impl.h:2050-2208, 2212-2271, 2309-2411).
  *
  * Conventions
  *   - Plain C, no exceptions cross the ABI. Every entry point returns an int
@@ -513,6 +516,95 @@ int ofhe_hip_bfv_mult_destroy(ofhe_bfv_mult_t handle);
 int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t handle, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
                            const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
                            void* stream);
+
+/* BFV multiplication by the BEHZ technique: LeveledSHEBFVRNS::EvalMult's
+ * `else` branches (bfvrns-leveledshe.cpp:275-297, 383-403) and the three
+ * DCRTPolyImpl functions under them, HAVE_INT128 && NATIVEINT == 64 branches,
+ * integers only:
+ *   FastBaseConvqToBskMontgomery  dcrtpoly-impl.h:2050-2208
+ *   FastRNSFloorq                 dcrtpoly-impl.h:2212-2271
+ *   FastBaseConvSK                dcrtpoly-impl.h:2309-2411
+ * All data is [batch][towers][N] 64-bit words.  "Bsk" is the size_b towers of
+ * B followed by msk: size_b + 1 towers (the reference always has size_b ==
+ * size_q; nothing here assumes it).  mtilde = 2^16.
+ * ofhe_behz_tables holds one host pointer per table of
+ * CryptoParametersBFVRNS::PrecomputeCRTTables' BEHZ part
+ * (bfvrns-cryptoparameters.cpp:665-851), row-major where two-dimensional,
+ * one word where scalar; Shoup and 128-bit Barrett constants are derived in
+ * create.  create uploads and waits (it cannot run under stream capture) and
+ * returns OFHE_ERR_ARG -- before it looks at ctx -- for a modulus that is
+ * even or not below 2^60, a Bsk modulus <= 2^16, a modulus repeated in
+ * q u Bsk, size_q or size_b of 0 or above 255 (the sums of that many products
+ * must fit 128 bits, the reference's DoubleNativeInt limit) or a NULL table.
+ * Every other call is stream-ordered, one fused kernel launch per reference
+ * function, and never synchronises:
+ *   ofhe_hip_behz_q_to_bsk  x [batch][size_q][N] -> out [batch][size_b+1][N],
+ *     both in coefficient form (dcrtpoly-impl.h:2098-2187 alone).
+ *   ofhe_hip_behz_expand  the whole FastBaseConvqToBskMontgomery with its
+ *     format handling (dcrtpoly-impl.h:2050-2208), as ofhe_hip_expand_crt_basis:
+ *     x [batch][size_q][N] (evaluation form when eval_form != 0, else
+ *     coefficient form) -> out [batch][size_q+size_b+1][N], evaluation form.
+ *     An evaluation-form input keeps its Q towers (its INTT passes through
+ *     out's Q slots); a coefficient-form input has them transformed; the Bsk
+ *     towers are always transformed.  out must not overlap x.
+ *   ofhe_hip_behz_floor  x [batch][size_q+size_b+1][N] -> out
+ *     [batch][size_b+1][N], coefficient form; x is only read (the reference
+ *     twists its Q towers in place and then discards them).
+ *   ofhe_hip_behz_conv_sk  x [batch][size_b+1][N] -> out [batch][size_q][N].
+ *     One deliberate definition: the correction is the CENTRED alpha,
+ *     out_j = (S_j - alpha_c B) mod q_j with alpha_c = alpha - msk for
+ *     alpha > floor(msk / 2).  The reference forms alpha.ModSubFast(msk, q_j)
+ *     = alpha + q_j - msk in unsigned words (dcrtpoly-impl.h:2384-2385), which
+ *     is that residue only while msk - alpha <= q_j and wraps for a ciphertext
+ *     tower below msk / 2; the two agree wherever the reference does not
+ *     wrap, in particular whenever msk < 2 min q_j.
+ *   ofhe_hip_behz_floor_sk  floor then conv_sk (bfvrns-leveledshe.cpp:390-401):
+ *     x [batch][size_q+size_b+1][N] -> out [batch][size_q][N].  fused = 1: one
+ *     launch that keeps the size_b + 1 intermediate residues of a coefficient
+ *     on chip (OFHE_ERR_ARG when size_b > OFHE_BEHZ_FUSED_MAX_B); 0: the two
+ *     launches through pool scratch; 2: fused when it fits, which is what the
+ *     multiplication does.  Same words either way; 0 and 1 exist, like the
+ *     kernel choices of ofhe_bconv_options, so that tests and A/B timings
+ *     reach both paths in one process.
+ *   ofhe_hip_bfv_eval_mult_behz  c0, c1, d0, d1 [batch][Q][N] evaluation form
+ *     -> out0..out2 [batch][Q][N] coefficient form, as ofhe_hip_bfv_eval_mult:
+ *     behz_expand of the four inputs, ofhe_hip_eval_mult_core over plan_qbsk
+ *     (Q towers then Bsk), INTT, floor and conv_sk (fused when it fits).
+ *     Scratch comes from the context's stream-ordered pool.
+ * The plans must transform exactly the handle's towers at its N in its
+ * context (OFHE_ERR_ARG otherwise). */
+#define OFHE_BEHZ_FUSED_MAX_B 16
+typedef struct ofhe_behz_s* ofhe_behz_t;
+typedef struct ofhe_behz_tables {
+    const uint64_t* tQHatInvModq;      /* [size_q]              :724-735 */
+    const uint64_t* QHatModbsk;        /* [size_q][size_b + 1]  :737-749 */
+    const uint64_t* QHatModmtilde;     /* [size_q]              :748 */
+    const uint64_t* qInvModbsk;        /* [size_q][size_b + 1]  :751-757 */
+    const uint64_t* mtildeQHatInvModq; /* [size_q]              :759-772 */
+    const uint64_t* negQInvModmtilde;  /* [1]                   :774-777 */
+    const uint64_t* QModbsk;           /* [size_b + 1]          :779-787 */
+    const uint64_t* mtildeInvModbsk;   /* [size_b + 1]          :789-797 */
+    const uint64_t* tQInvModbsk;       /* [size_b + 1]          :799-808 */
+    const uint64_t* BHatInvModb;       /* [size_b]              :810-821 */
+    const uint64_t* BHatModq;          /* [size_b][size_q]      :823-832 */
+    const uint64_t* BHatModmsk;        /* [size_b]              :834-839 */
+    const uint64_t* BInvModmsk;        /* [1]                   :841-843 */
+    const uint64_t* BModq;             /* [size_q]              :845-851 */
+} ofhe_behz_tables;
+int ofhe_hip_behz_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const uint64_t* q, uint32_t size_b,
+                         const uint64_t* bsk /* size_b + 1, msk last */, uint64_t t, const ofhe_behz_tables* tables,
+                         ofhe_behz_t* handle);
+int ofhe_hip_behz_destroy(ofhe_behz_t handle);
+int ofhe_hip_behz_q_to_bsk(ofhe_behz_t handle, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+int ofhe_hip_behz_expand(ofhe_behz_t handle, ofhe_plan_t plan_q, ofhe_plan_t plan_bsk, int eval_form,
+                         const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+int ofhe_hip_behz_floor(ofhe_behz_t handle, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+int ofhe_hip_behz_conv_sk(ofhe_behz_t handle, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
+int ofhe_hip_behz_floor_sk(ofhe_behz_t handle, int fused, const uint64_t* x, uint64_t* out, uint32_t batch,
+                           void* stream);
+int ofhe_hip_bfv_eval_mult_behz(ofhe_behz_t handle, ofhe_plan_t plan_q, ofhe_plan_t plan_bsk, ofhe_plan_t plan_qbsk,
+                                const uint64_t* c0, const uint64_t* c1, const uint64_t* d0, const uint64_t* d1,
+                                uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch, void* stream);
 
 /* ---- multi-GPU: evaluation-key broadcast over RCCL (xGMI) ----
  * the path shards by ciphertext batch with no exchange;

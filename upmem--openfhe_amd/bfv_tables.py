@@ -101,3 +101,45 @@ class BfvTables:
     @staticmethod
     def flat(rows) -> List[int]:
         return [v for row in rows for v in row]
+
+
+MTILDE = 1 << 16  # m_mtilde, the Montgomery modulus of the BEHZ base extension
+
+
+class BehzTables:
+    """The BEHZ tables of ``PrecomputeCRTTables`` (:665-851) for ciphertext towers q, auxiliary towers
+    b, the extra modulus msk and plaintext modulus t.  "bsk" is b followed by msk.  The class takes B
+    and msk as given (the reference chooses them at :674-703); Shoup and Barrett constants are not
+    tables of this class (the library derives them)."""
+
+    TABLES = ("tQHatInvModq", "QHatModbsk", "QHatModmtilde", "qInvModbsk", "mtildeQHatInvModq",
+              "negQInvModmtilde", "QModbsk", "mtildeInvModbsk", "tQInvModbsk", "BHatInvModb", "BHatModq",
+              "BHatModmsk", "BInvModmsk", "BModq")
+
+    def __init__(self, q: Sequence[int], b: Sequence[int], msk: int, t: int):
+        self.q, self.b, self.msk, self.t = [int(v) for v in q], [int(v) for v in b], int(msk), int(t)
+        self.bsk = self.b + [self.msk]
+        Q, B = product(self.q), product(self.b)
+        self.Q, self.B = Q, B
+        qhi = hat_inv(self.q)
+        self.tQHatInvModq = [h * self.t % m for h, m in zip(qhi, self.q)]            # :724-735
+        self.QHatModbsk = hat_mod(self.q, self.bsk)                                  # :737-747, [i][j]
+        self.QHatModmtilde = [Q // m % MTILDE for m in self.q]                       # :748
+        self.qInvModbsk = [[pow(m, -1, bj) for bj in self.bsk] for m in self.q]      # :751-757, [i][j]
+        self.mtildeQHatInvModq = [h * MTILDE % m for h, m in zip(qhi, self.q)]       # :759-772
+        self.negQInvModmtilde = (MTILDE - 1) * pow(Q, -1, MTILDE) % MTILDE           # :774-777
+        self.QModbsk = [Q % bj for bj in self.bsk]                                   # :779-787
+        self.mtildeInvModbsk = [pow(MTILDE % bj, -1, bj) for bj in self.bsk]         # :789-797
+        self.tQInvModbsk = [pow(Q, -1, bj) * self.t % bj for bj in self.bsk]         # :799-808
+        self.BHatInvModb = hat_inv(self.b)                                           # :810-821
+        self.BHatModq = hat_mod(self.b, self.q)                                      # :823-832, [i][j]
+        self.BHatModmsk = [B // bi % self.msk for bi in self.b]                      # :834-839
+        self.BInvModmsk = pow(B, -1, self.msk)                                       # :841-843
+        self.BModq = [B % m for m in self.q]                                         # :845-851
+
+    def flat(self, name: str) -> List[int]:
+        """the table as the flat row-major list of words the C ABI takes (a scalar as one word)"""
+        v = getattr(self, name)
+        if isinstance(v, int):
+            return [v]
+        return [w for row in v for w in row] if v and isinstance(v[0], list) else list(v)

@@ -1,8 +1,8 @@
 // internal.hpp -- definitions shared by the translation units of the backend
 // (ofhe_hip.hip: context, plans, NTT, element-wise ops, base conversion;
 // keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching, rescaling;
-// bfv.hip: BFV multiplication, ScaleAndRound; comm.hip: multi-device
-// collectives).
+// bfv.hip: BFV multiplication (HPS family), ScaleAndRound; behz.hip: BFV
+// multiplication (BEHZ); comm.hip: multi-device collectives).
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

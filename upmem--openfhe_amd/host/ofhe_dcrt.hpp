@@ -20,6 +20,11 @@
 //                             <- the BFV (HPS / HPSPOVERQ) multiplication steps
 //                                (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955,
 //                                bfvrns-leveledshe.cpp:168-408)
+//   BehzBasis                 <- the BFV (BEHZ) multiplication steps
+//                                FastBaseConvqToBskMontgomery, FastRNSFloorq,
+//                                FastBaseConvSK (dcrtpoly-impl.h:2050-2208,
+//                                2212-2271, 2309-2411, bfvrns-leveledshe.cpp:275-297,
+//                                383-403)
 //   KsCache / KeyCache        <- the per-parameter-set HYBRID tables
 //                                (rns-cryptoparameters.cpp:72-345) and the
 //                                evaluation keys kept resident on the device
@@ -925,6 +930,100 @@ private:
     ScaleAndRound sr_;
     std::unique_ptr<BaseConverter> neg_;
     ofhe_bfv_mult_t h_ = nullptr;
+};
+
+// The BEHZ tables as the reference's getters return them
+// (CryptoParametersBFVRNS, bfvrns-cryptoparameters.cpp:724-851): matrices
+// flattened row-major ([sizeQ][sizeBsk], [sizeB][sizeQ]).
+struct BehzTables {
+    std::vector<uint64_t> tQHatInvModq, QHatModbsk, QHatModmtilde, qInvModbsk, mtildeQHatInvModq;
+    uint64_t negQInvModmtilde = 0;
+    std::vector<uint64_t> QModbsk, mtildeInvModbsk, tQInvModbsk, BHatInvModb, BHatModq, BHatModmsk;
+    uint64_t BInvModmsk = 0;
+    std::vector<uint64_t> BModq;
+};
+
+// The BEHZ variant of the BFV multiplication (bfvrns-leveledshe.cpp:275-297,
+// 383-403) over Q, Bsk = B|msk and QBsk = Q|Bsk:
+//   FastBaseConvqToBskMontgomery  dcrtpoly-impl.h:2050-2208  Q (either format) -> Q|Bsk, EVALUATION
+//   FastRNSFloorq                 dcrtpoly-impl.h:2212-2271  Q|Bsk -> Bsk, COEFFICIENT
+//   FastBaseConvSK                dcrtpoly-impl.h:2309-2411  Bsk -> Q, COEFFICIENT (the centred
+//                                 correction, see ofhe_hip.h)
+//   BfvMultBehz                   EvalMult of two 2-element ciphertexts
+// The reference's members change the polynomial in place; these return the result.
+class BehzBasis {
+public:
+    BehzBasis(std::shared_ptr<DCRTParams> Q, std::shared_ptr<DCRTParams> Bsk, std::shared_ptr<DCRTParams> QBsk,
+              uint64_t t, const BehzTables& T)
+        : Q_(std::move(Q)), Bsk_(std::move(Bsk)), QBsk_(std::move(QBsk)) {
+        const size_t sq = Q_->Towers(), sk = Bsk_->Towers();
+        if (sk < 2 || QBsk_->Towers() != sq + sk) throw math_error("BehzBasis: QBsk must be Q's towers then Bsk's");
+        const size_t sb = sk - 1;
+        if (T.tQHatInvModq.size() != sq || T.QHatModbsk.size() != sq * sk || T.QHatModmtilde.size() != sq ||
+            T.qInvModbsk.size() != sq * sk || T.mtildeQHatInvModq.size() != sq || T.QModbsk.size() != sk ||
+            T.mtildeInvModbsk.size() != sk || T.tQInvModbsk.size() != sk || T.BHatInvModb.size() != sb ||
+            T.BHatModq.size() != sb * sq || T.BHatModmsk.size() != sb || T.BModq.size() != sq)
+            throw math_error("BehzBasis: table sizes do not match the bases");
+        const ofhe_behz_tables tb{T.tQHatInvModq.data(), T.QHatModbsk.data(),  T.QHatModmtilde.data(),
+                                  T.qInvModbsk.data(),   T.mtildeQHatInvModq.data(), &T.negQInvModmtilde,
+                                  T.QModbsk.data(),      T.mtildeInvModbsk.data(),   T.tQInvModbsk.data(),
+                                  T.BHatInvModb.data(),  T.BHatModq.data(),    T.BHatModmsk.data(),
+                                  &T.BInvModmsk,         T.BModq.data()};
+        check(ofhe_hip_behz_create(Q_->manager()->ctx(), Q_->LogN(), (uint32_t)sq, Q_->Moduli().data(), (uint32_t)sb,
+                                   Bsk_->Moduli().data(), t, &tb, &h_),
+              "BehzBasis");
+    }
+    ~BehzBasis() {
+        if (h_) ofhe_hip_behz_destroy(h_);
+    }
+    BehzBasis(const BehzBasis&) = delete;
+    BehzBasis& operator=(const BehzBasis&) = delete;
+
+    DCRTPolyHip FastBaseConvqToBskMontgomery(const DCRTPolyHip& x) const {
+        over(x, *Q_, "FastBaseConvqToBskMontgomery");
+        DCRTPolyHip out(QBsk_, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_behz_expand(h_, Q_->plan(), Bsk_->plan(), x.GetFormat() == Format::EVALUATION, x.data(),
+                                   out.data(), x.Batch(), nullptr),
+              "FastBaseConvqToBskMontgomery");
+        return out;
+    }
+    DCRTPolyHip FastRNSFloorq(const DCRTPolyHip& x) const {
+        over(x, *QBsk_, "FastRNSFloorq");
+        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("FastRNSFloorq: COEFFICIENT form expected");
+        DCRTPolyHip out(Bsk_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_behz_floor(h_, x.data(), out.data(), x.Batch(), nullptr), "FastRNSFloorq");
+        return out;
+    }
+    DCRTPolyHip FastBaseConvSK(const DCRTPolyHip& x) const {
+        over(x, *Bsk_, "FastBaseConvSK");
+        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("FastBaseConvSK: COEFFICIENT form expected");
+        DCRTPolyHip out(Q_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_behz_conv_sk(h_, x.data(), out.data(), x.Batch(), nullptr), "FastBaseConvSK");
+        return out;
+    }
+    // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
+    std::vector<DCRTPolyHip> BfvMultBehz(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
+                                         const DCRTPolyHip& d1) const {
+        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
+            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
+                v->Batch() != c0.Batch())
+                throw math_error("BfvMultBehz: EVALUATION-form ciphertexts over Q of one batch expected");
+        std::vector<DCRTPolyHip> out;
+        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_bfv_eval_mult_behz(h_, Q_->plan(), Bsk_->plan(), QBsk_->plan(), c0.data(), c1.data(), d0.data(),
+                                          d1.data(), out[0].data(), out[1].data(), out[2].data(), c0.Batch(), nullptr),
+              "BfvMultBehz");
+        return out;
+    }
+    ofhe_behz_t handle() const { return h_; }
+
+private:
+    static void over(const DCRTPolyHip& x, const DCRTParams& P, const char* what) {
+        if (x.GetParams()->Moduli() != P.Moduli() || x.GetParams()->LogN() != P.LogN())
+            throw math_error(std::string(what) + ": the polynomial is over another basis");
+    }
+    std::shared_ptr<DCRTParams> Q_, Bsk_, QBsk_;
+    ofhe_behz_t h_ = nullptr;
 };
 
 // ApproxModDown (dcrtpoly-impl.h:1134-1175): x over Q|P (EVALUATION) -> Q.

@@ -21,6 +21,9 @@ Host-side mirror of the reference's offload interface for the hot path:
   (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955) and ``LeveledSHEBFVRNS::EvalMult``
   for HPS / HPSPOVERQ (bfvrns-leveledshe.cpp:168-408); their tables come from
   ``bfv_tables.py``.
+* ``Behz`` ~ ``DCRTPolyImpl::FastBaseConvqToBskMontgomery`` / ``FastRNSFloorq`` / ``FastBaseConvSK``
+  (dcrtpoly-impl.h:2050-2208, 2212-2271, 2309-2411) and ``LeveledSHEBFVRNS::EvalMult`` for BEHZ
+  (bfvrns-leveledshe.cpp:275-297, 383-403); its tables are a ``bfv_tables.BehzTables``.
 * ``switch_modulus`` / ``NTTPlan.automorphism`` ~ ``NativeVectorT::SwitchModulus``
   (mubintvecnat.cpp:111-136) / ``PolyImpl::AutomorphismTransform`` (poly-impl.h:312-365).
 
@@ -149,6 +152,16 @@ _SIGS = {
                                                 ctypes.POINTER(_vp)]),
     "ofhe_hip_bfv_mult_destroy": (ctypes.c_int, [_vp]),
     "ofhe_hip_bfv_eval_mult": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_behz_create": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_uint32, _u64p,
+                                            ctypes.c_uint64, _vp, ctypes.POINTER(_vp)]),
+    "ofhe_hip_behz_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_behz_q_to_bsk": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_behz_expand": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_behz_floor": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_behz_conv_sk": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_behz_floor_sk": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_eval_mult_behz": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   ctypes.c_uint32, _vp]),
     "ofhe_hip_comm_unique_id": (ctypes.c_int, [_vp]),
     "ofhe_hip_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "ofhe_hip_comm_destroy": (ctypes.c_int, [_vp]),
@@ -156,6 +169,7 @@ _SIGS = {
 }
 
 COMM_ID_BYTES = 128  # OFHE_COMM_ID_BYTES
+BEHZ_FUSED_MAX_B = 16  # OFHE_BEHZ_FUSED_MAX_B: most B towers of the fused floor -> SK launch
 KS_ROT_CAP = 16  # rotations per launch of the hoisted-rotation calls (csrc/ks_kernels.hpp); more run in chunks
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -590,6 +604,77 @@ class BfvMult:
         """Inputs [batch][Q][N] evaluation form; outputs [batch][Q][N] coefficient form."""
         _check(lib().ofhe_hip_bfv_eval_mult(self._h, _vp(c0), _vp(c1), _vp(d0), _vp(d1), _vp(out0), _vp(out1),
                                             _vp(out2), int(batch), _vp(stream or None)))
+
+
+BEHZ_TWO_LAUNCHES, BEHZ_FUSED, BEHZ_AUTO = range(3)  # ofhe_hip_behz_floor_sk's `fused`
+
+
+class BehzTablesStruct(ctypes.Structure):
+    """ofhe_behz_tables: one host pointer per table, in the header's order"""
+    _fields_ = [(name, _u64p) for name in (
+        "tQHatInvModq", "QHatModbsk", "QHatModmtilde", "qInvModbsk", "mtildeQHatInvModq", "negQInvModmtilde",
+        "QModbsk", "mtildeInvModbsk", "tQInvModbsk", "BHatInvModb", "BHatModq", "BHatModmsk", "BInvModmsk",
+        "BModq")]
+
+
+class Behz:
+    """The BEHZ variant of the BFV multiplication for ciphertext towers T.q, auxiliary towers T.b and
+    T.msk (T: a ``bfv_tables.BehzTables``).  "Bsk" is the len(T.b) + 1 towers T.b + [T.msk].  Every
+    array is [batch][towers][N] words of device memory.
+
+    * ``q_to_bsk``   FastBaseConvqToBskMontgomery's conversion alone (dcrtpoly-impl.h:2098-2187):
+      [Q] -> [Bsk], coefficient form.
+    * ``expand``     the whole FastBaseConvqToBskMontgomery (2050-2208): [Q] -> [Q + Bsk], evaluation form.
+    * ``floor``      FastRNSFloorq (2212-2271): [Q + Bsk] -> [Bsk], coefficient form.
+    * ``conv_sk``    FastBaseConvSK (2309-2411) with the centred correction: [Bsk] -> [Q].
+    * ``floor_sk``   the two in one launch (BEHZ_FUSED), in two (BEHZ_TWO_LAUNCHES) or as the
+      multiplication chooses (BEHZ_AUTO): [Q + Bsk] -> [Q].
+    * ``eval_mult``  LeveledSHEBFVRNS::EvalMult, BEHZ (bfvrns-leveledshe.cpp:275-297, 383-403)."""
+
+    def __init__(self, ctx: Context, log_n: int, T):
+        self.ctx, self.log_n, self.tables = ctx, int(log_n), T
+        self.size_q, self.size_b = len(T.q), len(T.b)
+        self._keep = {name: _arr(T.flat(name)) for name in T.TABLES}
+        ts = BehzTablesStruct(**{name: ctypes.cast(a, _u64p) for name, a in self._keep.items()})
+        h = _vp()
+        _check(lib().ofhe_hip_behz_create(ctx.handle, self.log_n, self.size_q, _arr(T.q), self.size_b, _arr(T.bsk),
+                                          int(T.t), ctypes.cast(ctypes.byref(ts), _vp), ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(lib().ofhe_hip_behz_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def q_to_bsk(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_behz_q_to_bsk(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def expand(self, plan_q: NTTPlan, plan_bsk: NTTPlan, eval_form: bool, x: int, out: int, batch: int = 1,
+               stream: int = 0) -> None:
+        _check(lib().ofhe_hip_behz_expand(self._h, plan_q.handle, plan_bsk.handle, 1 if eval_form else 0, _vp(x),
+                                          _vp(out), int(batch), _vp(stream or None)))
+
+    def floor(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_behz_floor(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def conv_sk(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_behz_conv_sk(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def floor_sk(self, x: int, out: int, batch: int = 1, stream: int = 0, fused: int = BEHZ_AUTO) -> None:
+        _check(lib().ofhe_hip_behz_floor_sk(self._h, int(fused), _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def eval_mult(self, plan_q: NTTPlan, plan_bsk: NTTPlan, plan_qbsk: NTTPlan, c0: int, c1: int, d0: int, d1: int,
+                  out0: int, out1: int, out2: int, batch: int = 1, stream: int = 0) -> None:
+        """Inputs [batch][Q][N] evaluation form; outputs [batch][Q][N] coefficient form."""
+        _check(lib().ofhe_hip_bfv_eval_mult_behz(self._h, plan_q.handle, plan_bsk.handle, plan_qbsk.handle, _vp(c0),
+                                                 _vp(c1), _vp(d0), _vp(d1), _vp(out0), _vp(out1), _vp(out2),
+                                                 int(batch), _vp(stream or None)))
 
 
 def approx_mod_down(plan_q: NTTPlan, plan_p: NTTPlan, p_to_q: BaseConverter, p_inv_modq: Sequence[int], t: int,
