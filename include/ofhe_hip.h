@@ -506,7 +506,8 @@ int ofhe_hip_scale_and_round(ofhe_scale_round_t handle, const uint64_t* x, uint6
  * Scratch comes from the context's stream-ordered pool; no call synchronises. */
 enum {
     OFHE_BFV_HPS = 0,
-    OFHE_BFV_HPSPOVERQ = 1
+    OFHE_BFV_HPSPOVERQ = 1,
+    OFHE_BFV_BEHZ = 2 /* ofhe_hip_bfv_decrypt_create only; the multiplication is ofhe_hip_bfv_eval_mult_behz */
 };
 typedef struct ofhe_bfv_mult_s* ofhe_bfv_mult_t;
 int ofhe_hip_bfv_mult_create(ofhe_ctx_t ctx, int technique, ofhe_plan_t plan_q, ofhe_plan_t plan_r,
@@ -605,6 +606,115 @@ int ofhe_hip_behz_floor_sk(ofhe_behz_t handle, int fused, const uint64_t* x, uin
 int ofhe_hip_bfv_eval_mult_behz(ofhe_behz_t handle, ofhe_plan_t plan_q, ofhe_plan_t plan_bsk, ofhe_plan_t plan_qbsk,
                                 const uint64_t* c0, const uint64_t* c1, const uint64_t* d0, const uint64_t* d1,
                                 uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch, void* stream);
+
+/* ---- BFV decryption and encryption scaling: PKEBFVRNS::Decrypt
+ *      (pke/lib/scheme/bfvrns/bfvrns-pke.cpp:205-248) and the one BFV-specific
+ *      step of encryption, DCRTPolyImpl::TimesQovert
+ *      (dcrtpoly-impl.h:1015-1031), so that only the N-word plaintext crosses
+ *      the bus.  Bit-exact with the reference's NATIVEINT == 64 build.
+ *
+ *      Floating-point contract (the reference's decryption ScaleAndRound uses
+ *      double throughout, dcrtpoly-impl.h:1537-1814; the contract of the HPS
+ *      block above applies unchanged).  The reference chooses one of eight
+ *      loops (dcrtpoly-impl.h:1547-1803), labelled A-H in
+ *      UnitTestBFVrnsDecrypt.cpp:126-148, from qMSB = msb(q[0]), tMSB,
+ *      sizeQMSB = GetMSB64(size_q), qMSBHf = qMSB >> 1 and whether t is a power
+ *      of two; the library chooses the same one:
+ *        t = 2^k:  qMSB + sizeQMSB < 52:  qMSB + tMSB + sizeQMSB < 63 ? A : B
+ *                  else:                  qMSBHf + tMSB + sizeQMSB < 62 ? C : D
+ *        else:     qMSB + sizeQMSB < 52:  qMSB + tMSB + sizeQMSB < 52 ? E : F
+ *                  else:                  qMSBHf + tMSB + sizeQMSB < 52 ? G : H
+ *      A-D: floatSum starts at 0.5; per tower, in order,
+ *        floatSum = floatSum + (double(x_i) * frac[i]);
+ *      in the split loops C and D this is done for lo = x_i - (hi << qMSBHf)
+ *      with frac[i], then for hi = x_i >> qMSBHf with fracB[i].
+ *        out = (intSum + uint64(floatSum)) & (t - 1)
+ *      with intSum modulo 2^64 (A and B give the same word, and so do C and D).
+ *      E-H: floatSum starts at 0.0, the same chain; intSum is the exact sum of
+ *      the products x_i * table[i] in E and G and the sum of the products
+ *      reduced mod t (ModMulFastConst) in F and H -- the two give different
+ *      doubles, so the loop matters; then
+ *        floatSum = floatSum + double(intSum)
+ *        quot     = uint64(floatSum * tInv)          tInv = 1.0 / td, td = double(t)
+ *        floatSum = floatSum - (td * double(quot))
+ *        out      = uint64(floatSum + 0.5)
+ *      written as computed: it may equal t, as the reference's may, and is not
+ *      canonicalised.  Every multiply, add and subtract is rounded separately
+ *      to IEEE double, round-to-nearest-even; nothing is fused or reordered;
+ *      double(uint64) is the correctly rounded conversion.  The casts to
+ *      uint64 are the reference's: of a negative double they are undefined
+ *      there (and give 0 here).
+ *      One tower (size_q == 1, either technique; bfvrns-pke.cpp:233-245,
+ *      mubintvecnat.cpp:420-435, ubintnat.h:536-540): with
+ *        MR(y) = uint64(double(t) * (double(y) / double(q)) + 0.5)
+ *      -- one correctly rounded IEEE division, then a separate multiply and
+ *      add -- r = x > (q >> 1) ? q - MR(q - x) : MR(x) mod q, and out =
+ *      SwitchModulus(r, q -> t) as ofhe_hip_switch_modulus.
+ *      BEHZ (dcrtpoly-impl.h:2005-2049) is integers only, gamma = 2^26
+ *      (rns-cryptoparameters.h:1701): per tower y = x_i tgammaQHatInvModq[i] mod
+ *      q_i, s = (s + y negInvqModtgamma[i] mod tgamma) mod tgamma; out =
+ *      (s + (s & (2^26 - 1))) >> 26.
+ *
+ * ofhe_bfv_decrypt_tables holds one host pointer per table of
+ * CryptoParametersBFVRNS::PrecomputeCRTTables (bfvrns-cryptoparameters.cpp):
+ * the HPS family reads the first four (:446-495; the two B tables only when
+ * qMSB + sizeQMSB >= 52), BEHZ the next two (:853-884); tInvModq and negQModt
+ * (:87-94) serve ofhe_hip_times_q_over_t and may both be NULL.  Tables a
+ * technique does not read may be NULL, and none is read when size_q == 1.
+ * Shoup preconditioners, td and tInv are derived in create, which uploads once
+ * and waits (it cannot run under stream capture) and returns OFHE_ERR_ARG --
+ * before it looks at ctx -- for t < 2, size_q of 0 or above 255,
+ * 2 size_q t >= 2^64 (the sums of reduced products could wrap), a modulus that
+ * is even or not below 2^60, BEHZ with t 2^26 >= 2^58, or a missing table (a
+ * missing B table when the split applies included).  Every other call is
+ * stream-ordered and never synchronises. */
+enum {
+    OFHE_BFV_DECRYPT_BEHZ = 8,     /* ofhe_hip_bfv_decrypt_branch: after the loops A..H = 0..7 */
+    OFHE_BFV_DECRYPT_ONE_TOWER = 9
+};
+typedef struct ofhe_bfv_decrypt_s* ofhe_bfv_decrypt_t;
+typedef struct ofhe_bfv_decrypt_tables {
+    const uint64_t* tQHatInvModqDivqModt;  /* [size_q]  :453-462, 480 */
+    const uint64_t* tQHatInvModqBDivqModt; /* [size_q]  :487-489 */
+    const double* tQHatInvModqDivqFrac;    /* [size_q]  :465-467, 483-485 */
+    const double* tQHatInvModqBDivqFrac;   /* [size_q]  :492-493 */
+    const uint64_t* tgammaQHatInvModq;     /* [size_q]  :871-884 */
+    const uint64_t* negInvqModtgamma;      /* [size_q]  :859-869 */
+    const uint64_t* tInvModq;              /* [size_q]  :87-90 */
+    const uint64_t* negQModt;              /* [1]       :92-94 */
+} ofhe_bfv_decrypt_tables;
+int ofhe_hip_bfv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const uint64_t* q, uint64_t t,
+                                int technique, const ofhe_bfv_decrypt_tables* tables, ofhe_bfv_decrypt_t* handle);
+int ofhe_hip_bfv_decrypt_destroy(ofhe_bfv_decrypt_t handle);
+/* The loop the handle runs: 0..7 for A..H (dcrtpoly-impl.h:1547-1803),
+ * OFHE_BFV_DECRYPT_BEHZ, or OFHE_BFV_DECRYPT_ONE_TOWER when size_q == 1. */
+int ofhe_hip_bfv_decrypt_branch(ofhe_bfv_decrypt_t handle, int* branch);
+/* DCRTPolyImpl::ScaleAndRound to a NativePoly mod t (dcrtpoly-impl.h:1537-1814
+ * for the HPS family, 2005-2049 for BEHZ; bfvrns-pke.cpp:233-245 when size_q ==
+ * 1): x [batch][size_q][N] in coefficient form -> out [batch][N].  One kernel,
+ * one thread per (batch entry, coefficient): (size_q + 1) * 8 bytes move per
+ * coefficient. */
+int ofhe_hip_bfv_decrypt_scale_round(ofhe_bfv_decrypt_t handle, const uint64_t* x, uint64_t* out, uint32_t batch,
+                                     void* stream);
+/* PKEBFVRNS::Decrypt (bfvrns-pke.cpp:205-248) with PKERNS::DecryptCore
+ * (rns-pke.cpp:199-224): `elements` (2 or 3) ciphertext elements c0, c1 (, c2),
+ * each [batch][size_q][N], all in evaluation form (eval_form != 0) or all in
+ * coefficient form (as ofhe_hip_bfv_eval_mult leaves them), and the secret key
+ * s [size_q][N] in evaluation form, shared by the batch -> out [batch][N].
+ * Coefficient-form elements are transformed first; one launch forms
+ * b = c0 + c1 s (+ c2 s^2) towerwise with canonical results (s^2 in the
+ * kernel); INTT through plan_q; the scale-round kernel.  The ciphertext must
+ * have as many towers as the key (no HPSPOVERQLEVELED levels).  plan_q must
+ * transform exactly the handle's towers at its N in its context.  Scratch
+ * comes from the context's stream-ordered pool. */
+int ofhe_hip_bfv_decrypt(ofhe_bfv_decrypt_t handle, ofhe_plan_t plan_q, uint32_t elements, int eval_form,
+                         const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* s, uint64_t* out,
+                         uint32_t batch, void* stream);
+/* DCRTPolyImpl::TimesQovert (dcrtpoly-impl.h:1015-1031): out_i =
+ * ((x_i negQModt) mod t) tInvModq[i] mod q_i over [batch][size_q][N], canonical
+ * for any 64-bit x_i; out may be x.  OFHE_ERR_STATE when the handle was created
+ * without tInvModq / negQModt. */
+int ofhe_hip_times_q_over_t(ofhe_bfv_decrypt_t handle, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
 
 /* ---- multi-GPU: evaluation-key broadcast over RCCL (xGMI) ----
  * the path shards by ciphertext batch with no exchange;

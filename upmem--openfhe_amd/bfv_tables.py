@@ -4,7 +4,7 @@ integers and floats only (no device, no native library).
 A restatement of ``CryptoParametersBFVRNS::PrecomputeCRTTables``
 (pke/lib/scheme/bfvrns/bfvrns-cryptoparameters.cpp) for the full level: every
 table the calls of ``ofhe_hip.py`` (``BaseConverter``, ``ScaleRound``,
-``BfvMult``) take.  The reference's line numbers are cited at each table.
+``BfvMult``, ``Behz``, ``BfvDecrypt``) take.  The reference's line numbers are cited at each table.
 
 The fractional tables are ``float(X mod s_i) / float(s_i)``: the reference's
 expression (two correctly rounded conversions and one IEEE division), not a
@@ -143,3 +143,56 @@ class BehzTables:
         if isinstance(v, int):
             return [v]
         return [w for row in v for w in row] if v and isinstance(v[0], list) else list(v)
+
+
+BEHZ = 2          # the decryption handle's technique next to HPS / HPSPOVERQ
+GAMMA_BITS = 26   # m_gamma = 2^26 (rns-cryptoparameters.h:1701)
+BRANCHES = "ABCDEFGH"  # the reference's labels of ScaleAndRound's eight loops (UnitTestBFVrnsDecrypt.cpp:126-148)
+
+
+def decrypt_branch(size_q: int, q0: int, t: int) -> int:
+    """Which of the eight loops DCRTPolyImpl::ScaleAndRound -> NativePoly takes (dcrtpoly-impl.h:1547-1803), as
+    an index into BRANCHES: MSB is the bit length (GetMSB), qMSB that of q[0]."""
+    q_msb, t_msb, s_msb = int(q0).bit_length(), int(t).bit_length(), int(size_q).bit_length()
+    pow2 = t & (t - 1) == 0
+    split = q_msb + s_msb >= 52
+    bits = ((q_msb >> 1) if split else q_msb) + t_msb + s_msb
+    reduced = bits >= ((62 if split else 63) if pow2 else 52)
+    return (0 if pow2 else 4) + (2 if split else 0) + (1 if reduced else 0)
+
+
+class DecryptTables:
+    """The tables of decryption and of TimesQovert for ciphertext towers q and plaintext modulus t, from
+    ``PrecomputeCRTTables`` (bfvrns-cryptoparameters.cpp): with X_i = t ((Q / q_i)^-1 mod q_i),
+
+    * tQHatInvModqDivqModt[i] = floor(X_i / q_i) mod t, tQHatInvModqDivqFrac[i] = double(X_i mod q_i) /
+      double(q_i)                                                                       (:453-485)
+    * the same for X_i 2^qMSBHf: tQHatInvModqBDivqModt / Frac; the reference fills them only when
+      qMSB + sizeQMSB >= 52 (``split``), this class always                              (:474-493)
+    * tgamma = t 2^26, negInvqModtgamma[i] = -(q_i^-1) mod tgamma, tgammaQHatInvModq[i] =
+      t 2^26 (Q / q_i)^-1 mod q_i                                                       (:853-884)
+    * tInvModq[i] = t^-1 mod q_i, negQModt = t - (Q mod t)                              (:87-94)
+
+    ``branch`` is the loop the reference takes (an index into BRANCHES)."""
+
+    TABLES = ("tQHatInvModqDivqModt", "tQHatInvModqBDivqModt", "tQHatInvModqDivqFrac", "tQHatInvModqBDivqFrac",
+              "tgammaQHatInvModq", "negInvqModtgamma", "tInvModq", "negQModt")
+
+    def __init__(self, q: Sequence[int], t: int):
+        self.q, self.t = [int(v) for v in q], int(t)
+        Q = product(self.q)
+        self.Q = Q
+        self.q_msb_hf = self.q[0].bit_length() >> 1
+        self.branch = decrypt_branch(len(self.q), self.q[0], self.t)
+        self.split = bool(self.branch & 2)
+        X = [self.t * h for h in hat_inv(self.q)]
+        XB = [x << self.q_msb_hf for x in X]
+        self.tQHatInvModqDivqModt = [x // m % self.t for x, m in zip(X, self.q)]
+        self.tQHatInvModqDivqFrac = [float(x % m) / float(m) for x, m in zip(X, self.q)]
+        self.tQHatInvModqBDivqModt = [x // m % self.t for x, m in zip(XB, self.q)]
+        self.tQHatInvModqBDivqFrac = [float(x % m) / float(m) for x, m in zip(XB, self.q)]
+        self.tgamma = self.t << GAMMA_BITS
+        self.negInvqModtgamma = [(self.tgamma - 1) * pow(m, -1, self.tgamma) % self.tgamma for m in self.q]
+        self.tgammaQHatInvModq = [h * (1 << GAMMA_BITS) % m * self.t % m for h, m in zip(hat_inv(self.q), self.q)]
+        self.tInvModq = [pow(self.t, -1, m) for m in self.q]
+        self.negQModt = self.t - Q % self.t

@@ -2,7 +2,8 @@
 // (ofhe_hip.hip: context, plans, NTT, element-wise ops, base conversion;
 // keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching, rescaling;
 // bfv.hip: BFV multiplication (HPS family), ScaleAndRound; behz.hip: BFV
-// multiplication (BEHZ); comm.hip: multi-device collectives).
+// multiplication (BEHZ); bfv_decrypt.hip: BFV decryption, TimesQovert; comm.hip:
+// multi-device collectives).
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

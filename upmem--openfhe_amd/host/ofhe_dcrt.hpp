@@ -444,6 +444,8 @@ enum class Format { EVALUATION = 0, COEFFICIENT = 1 };
 // tower it is also the PimData op set (PimData.h:46-168: + - * and
 // ModAdd/ModSub/ModMul with vector or scalar right-hand sides).
 // ---------------------------------------------------------------------------
+class BfvDecrypt;
+
 class DCRTPolyHip {
 public:
     DCRTPolyHip(std::shared_ptr<DCRTParams> p, Format f, uint32_t batch = 1)
@@ -549,6 +551,10 @@ public:
               "ModReduce");
         *this = std::move(r);
     }
+
+    // TimesQovert (dcrtpoly-impl.h:1015-1031), in place, with the tInvModq and
+    // negQModt of d's tables (defined after BfvDecrypt)
+    inline void TimesQovert(const BfvDecrypt& d);
 
     // Times(const std::vector<NativeInteger>&): one scalar per tower (Shoup)
     DCRTPolyHip Times(const std::vector<uint64_t>& scalars) const {
@@ -1025,6 +1031,102 @@ private:
     std::shared_ptr<DCRTParams> Q_, Bsk_, QBsk_;
     ofhe_behz_t h_ = nullptr;
 };
+
+// The decryption tables as the reference's getters return them
+// (CryptoParametersBFVRNS, bfvrns-cryptoparameters.cpp:87-94, 446-495, 853-884).
+// The HPS family reads the first four (the two B tables only where the reference
+// fills them), BEHZ the next two; tInvModq / negQModt serve TimesQovert.  A
+// table the technique does not read may stay empty.
+struct BfvDecryptTables {
+    std::vector<uint64_t> tQHatInvModqDivqModt, tQHatInvModqBDivqModt;
+    std::vector<double> tQHatInvModqDivqFrac, tQHatInvModqBDivqFrac;
+    std::vector<uint64_t> tgammaQHatInvModq, negInvqModtgamma, tInvModq;
+    uint64_t negQModt = 0;
+};
+
+// PKEBFVRNS::Decrypt (bfvrns-pke.cpp:205-248) over Q for plaintext modulus t
+// and technique OFHE_BFV_HPS / OFHE_BFV_HPSPOVERQ / OFHE_BFV_BEHZ:
+//   ScaleAndRound  dcrtpoly-impl.h:1537-1814 / 2005-2049 (one tower: bfvrns-pke.cpp:233-245)
+//                  Q, COEFFICIENT -> the batch * N words mod t, on the host
+//   Decrypt        DecryptCore (rns-pke.cpp:199-224), INTT, ScaleAndRound: cv = 2 or 3
+//                  elements over Q, all in one format; s the secret key, EVALUATION, batch 1
+class BfvDecrypt {
+public:
+    BfvDecrypt(std::shared_ptr<DCRTParams> Q, uint64_t t, int technique, const BfvDecryptTables& T)
+        : Q_(std::move(Q)) {
+        const size_t sq = Q_->Towers();
+        for (const auto* v : {&T.tQHatInvModqDivqModt, &T.tQHatInvModqBDivqModt, &T.tgammaQHatInvModq,
+                              &T.negInvqModtgamma, &T.tInvModq})
+            if (!v->empty() && v->size() != sq) throw math_error("BfvDecrypt: table sizes do not match the basis");
+        for (const auto* v : {&T.tQHatInvModqDivqFrac, &T.tQHatInvModqBDivqFrac})
+            if (!v->empty() && v->size() != sq) throw math_error("BfvDecrypt: table sizes do not match the basis");
+        auto ptr = [](const auto& v) { return v.empty() ? nullptr : v.data(); };
+        const ofhe_bfv_decrypt_tables tb{ptr(T.tQHatInvModqDivqModt), ptr(T.tQHatInvModqBDivqModt),
+                                         ptr(T.tQHatInvModqDivqFrac), ptr(T.tQHatInvModqBDivqFrac),
+                                         ptr(T.tgammaQHatInvModq),    ptr(T.negInvqModtgamma),
+                                         ptr(T.tInvModq),             T.tInvModq.empty() ? nullptr : &T.negQModt};
+        check(ofhe_hip_bfv_decrypt_create(Q_->manager()->ctx(), Q_->LogN(), (uint32_t)sq, Q_->Moduli().data(), t,
+                                          technique, &tb, &h_),
+              "BfvDecrypt");
+    }
+    ~BfvDecrypt() {
+        if (h_) ofhe_hip_bfv_decrypt_destroy(h_);
+    }
+    BfvDecrypt(const BfvDecrypt&) = delete;
+    BfvDecrypt& operator=(const BfvDecrypt&) = delete;
+
+    // the loop that runs: 0..7 for A..H, OFHE_BFV_DECRYPT_BEHZ, OFHE_BFV_DECRYPT_ONE_TOWER
+    int Branch() const {
+        int b = -1;
+        check(ofhe_hip_bfv_decrypt_branch(h_, &b), "BfvDecrypt::Branch");
+        return b;
+    }
+    std::vector<uint64_t> ScaleAndRound(const DCRTPolyHip& x) const {
+        over(x, "ScaleAndRound");
+        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("ScaleAndRound: COEFFICIENT form expected");
+        DeviceBuffer out(Q_->manager(), (size_t)x.Batch() * Q_->GetRingDimension());
+        check(ofhe_hip_bfv_decrypt_scale_round(h_, x.data(), out.get(), x.Batch(), nullptr), "ScaleAndRound");
+        return fetch(out);
+    }
+    std::vector<uint64_t> Decrypt(const std::vector<DCRTPolyHip>& cv, const DCRTPolyHip& s) const {
+        if (cv.size() != 2 && cv.size() != 3) throw math_error("Decrypt: 2 or 3 ciphertext elements expected");
+        for (const auto& c : cv) {
+            over(c, "Decrypt");
+            if (c.GetFormat() != cv[0].GetFormat() || c.Batch() != cv[0].Batch())
+                throw math_error("Decrypt: elements of one format and one batch expected");
+        }
+        over(s, "Decrypt");
+        if (s.GetFormat() != Format::EVALUATION || s.Batch() != 1)
+            throw math_error("Decrypt: the secret key in EVALUATION form, batch 1, expected");
+        DeviceBuffer out(Q_->manager(), (size_t)cv[0].Batch() * Q_->GetRingDimension());
+        check(ofhe_hip_bfv_decrypt(h_, Q_->plan(), (uint32_t)cv.size(), cv[0].GetFormat() == Format::EVALUATION,
+                                   cv[0].data(), cv[1].data(), cv.size() == 3 ? cv[2].data() : nullptr, s.data(),
+                                   out.get(), cv[0].Batch(), nullptr),
+              "Decrypt");
+        return fetch(out);
+    }
+    const std::shared_ptr<DCRTParams>& GetParams() const { return Q_; }
+    ofhe_bfv_decrypt_t handle() const { return h_; }
+
+private:
+    void over(const DCRTPolyHip& x, const char* what) const {
+        if (x.GetParams()->Moduli() != Q_->Moduli() || x.GetParams()->LogN() != Q_->LogN())
+            throw math_error(std::string(what) + ": the polynomial is over another basis");
+    }
+    static std::vector<uint64_t> fetch(const DeviceBuffer& d) {
+        std::vector<uint64_t> h(d.size());
+        d.download(h.data());
+        return h;
+    }
+    std::shared_ptr<DCRTParams> Q_;
+    ofhe_bfv_decrypt_t h_ = nullptr;
+};
+
+inline void DCRTPolyHip::TimesQovert(const BfvDecrypt& d) {
+    if (p_->Moduli() != d.GetParams()->Moduli() || p_->LogN() != d.GetParams()->LogN())
+        throw math_error("TimesQovert: the polynomial is over another basis");
+    check(ofhe_hip_times_q_over_t(d.handle(), data(), data(), batch_, nullptr), "TimesQovert");
+}
 
 // ApproxModDown (dcrtpoly-impl.h:1134-1175): x over Q|P (EVALUATION) -> Q.
 inline DCRTPolyHip ApproxModDown(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsQ,

@@ -24,6 +24,10 @@ Host-side mirror of the reference's offload interface for the hot path:
 * ``Behz`` ~ ``DCRTPolyImpl::FastBaseConvqToBskMontgomery`` / ``FastRNSFloorq`` / ``FastBaseConvSK``
   (dcrtpoly-impl.h:2050-2208, 2212-2271, 2309-2411) and ``LeveledSHEBFVRNS::EvalMult`` for BEHZ
   (bfvrns-leveledshe.cpp:275-297, 383-403); its tables are a ``bfv_tables.BehzTables``.
+* ``BfvDecrypt`` ~ ``PKEBFVRNS::Decrypt`` (bfvrns-pke.cpp:205-248): ``PKERNS::DecryptCore``
+  (rns-pke.cpp:199-224), the two ``ScaleAndRound`` overloads to a ``NativePoly`` mod t
+  (dcrtpoly-impl.h:1537-1814, 2005-2049), the one-tower ``MultiplyAndRound`` path, and
+  ``DCRTPolyImpl::TimesQovert`` (dcrtpoly-impl.h:1015-1031); its tables are a ``bfv_tables.DecryptTables``.
 * ``switch_modulus`` / ``NTTPlan.automorphism`` ~ ``NativeVectorT::SwitchModulus``
   (mubintvecnat.cpp:111-136) / ``PolyImpl::AutomorphismTransform`` (poly-impl.h:312-365).
 
@@ -162,6 +166,14 @@ _SIGS = {
     "ofhe_hip_behz_floor_sk": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_bfv_eval_mult_behz": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_decrypt_create": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_uint64,
+                                                   ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "ofhe_hip_bfv_decrypt_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_bfv_decrypt_branch": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "ofhe_hip_bfv_decrypt_scale_round": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.c_uint32, _vp]),
+    "ofhe_hip_times_q_over_t": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_comm_unique_id": (ctypes.c_int, [_vp]),
     "ofhe_hip_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "ofhe_hip_comm_destroy": (ctypes.c_int, [_vp]),
@@ -675,6 +687,87 @@ class Behz:
         _check(lib().ofhe_hip_bfv_eval_mult_behz(self._h, plan_q.handle, plan_bsk.handle, plan_qbsk.handle, _vp(c0),
                                                  _vp(c1), _vp(d0), _vp(d1), _vp(out0), _vp(out1), _vp(out2),
                                                  int(batch), _vp(stream or None)))
+
+
+BFV_BEHZ = 2  # OFHE_BFV_BEHZ: BfvDecrypt's technique next to BFV_HPS / BFV_HPSPOVERQ
+BFV_DECRYPT_BEHZ, BFV_DECRYPT_ONE_TOWER = 8, 9  # BfvDecrypt.branch after the loops A..H = 0..7
+
+
+class BfvDecryptTablesStruct(ctypes.Structure):
+    """ofhe_bfv_decrypt_tables: one host pointer per table, in the header's order"""
+    _fields_ = [("tQHatInvModqDivqModt", _u64p), ("tQHatInvModqBDivqModt", _u64p),
+                ("tQHatInvModqDivqFrac", ctypes.POINTER(ctypes.c_double)),
+                ("tQHatInvModqBDivqFrac", ctypes.POINTER(ctypes.c_double)), ("tgammaQHatInvModq", _u64p),
+                ("negInvqModtgamma", _u64p), ("tInvModq", _u64p), ("negQModt", _u64p)]
+
+
+class BfvDecrypt:
+    """PKEBFVRNS::Decrypt (bfvrns-pke.cpp:205-248) and DCRTPolyImpl::TimesQovert for ciphertext towers T.q and
+    plaintext modulus T.t (T: a ``bfv_tables.DecryptTables``), technique BFV_HPS / BFV_HPSPOVERQ or BFV_BEHZ.
+    Tables the technique does not read, and members of T that are None, are not passed.
+
+    * ``scale_round``      ScaleAndRound to t: x [batch][Q][N] coefficient form -> out [batch][N].
+    * ``decrypt``          DecryptCore, INTT, ScaleAndRound: 2 or 3 elements [batch][Q][N] and the secret key
+      [Q][N] (evaluation form) -> out [batch][N].
+    * ``times_q_over_t``   TimesQovert over [batch][Q][N]; out may be x.
+    * ``branch``           the loop that runs: 0..7 for A..H, BFV_DECRYPT_BEHZ, BFV_DECRYPT_ONE_TOWER."""
+
+    def __init__(self, ctx: Context, log_n: int, T, technique: int = BFV_HPS):
+        self.ctx, self.log_n, self.tables, self.technique = ctx, int(log_n), T, int(technique)
+        self.size_q = len(T.q)
+        behz = self.technique == BFV_BEHZ
+        names = ["tInvModq", "negQModt"]
+        if self.size_q > 1:
+            names += ["tgammaQHatInvModq", "negInvqModtgamma"] if behz else \
+                ["tQHatInvModqDivqModt", "tQHatInvModqDivqFrac"] + \
+                (["tQHatInvModqBDivqModt", "tQHatInvModqBDivqFrac"] if T.split else [])
+        self._keep = {}
+        for name in names:
+            v = getattr(T, name)
+            if v is None:
+                continue
+            if name.endswith("Frac"):
+                self._keep[name] = (ctypes.c_double * len(v))(*[float(f) for f in v])
+            else:
+                self._keep[name] = _arr([v] if isinstance(v, int) else v)
+        ts = BfvDecryptTablesStruct(**{n: ctypes.cast(a, dict(BfvDecryptTablesStruct._fields_)[n])
+                                       for n, a in self._keep.items()})
+        h = _vp()
+        _check(lib().ofhe_hip_bfv_decrypt_create(ctx.handle if ctx is not None else None, self.log_n, self.size_q,
+                                                 _arr(T.q), int(T.t), self.technique,
+                                                 ctypes.cast(ctypes.byref(ts), _vp), ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(lib().ofhe_hip_bfv_decrypt_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def branch(self) -> int:
+        b = ctypes.c_int(-1)
+        _check(lib().ofhe_hip_bfv_decrypt_branch(self._h, ctypes.byref(b)))
+        return b.value
+
+    def scale_round(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_bfv_decrypt_scale_round(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def decrypt(self, plan_q: NTTPlan, elements: Sequence[int], s: int, out: int, eval_form: bool, batch: int = 1,
+                stream: int = 0) -> None:
+        """elements: the 2 or 3 device pointers c0, c1 (, c2)."""
+        c = [int(p) for p in elements] + [0] * (3 - len(elements))
+        _check(lib().ofhe_hip_bfv_decrypt(self._h, plan_q.handle, len(elements), 1 if eval_form else 0, _vp(c[0]),
+                                          _vp(c[1]), _vp(c[2] or None), _vp(s), _vp(out), int(batch),
+                                          _vp(stream or None)))
+
+    def times_q_over_t(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        _check(lib().ofhe_hip_times_q_over_t(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
 
 
 def approx_mod_down(plan_q: NTTPlan, plan_p: NTTPlan, p_to_q: BaseConverter, p_inv_modq: Sequence[int], t: int,
