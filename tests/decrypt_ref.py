@@ -15,6 +15,9 @@ Python integers:
 ``scale_round_scalar(..., fused=True)`` is NOT the reference: its floating chain
 computes every a * b + c exactly (fractions.Fraction) and rounds once, which is
 what a contracted multiply-add gives.  The sensitivity test needs it.
+``tables_by_tower`` (the loop and the split point taken from another tower than
+q[0]) is not the reference either; ``one_tower_scalar`` restates ``one_tower``
+on one value and names the path it took.  tests/test_decrypt_cases.py needs both.
 
 The reference's cast of a negative double to uint64 is undefined, so
 ``scale_round`` asserts floatSum + 0.5 >= 0 before the final cast of the loops
@@ -22,6 +25,7 @@ E-H; ``case`` replaces any input that would violate it (none has been met).
 
 Polynomials are uint64 arrays [batch][towers][n].
 """
+import copy
 from fractions import Fraction
 
 import numpy as np
@@ -260,6 +264,53 @@ def planted_values(rng, Q, t, count):
 
 def fused_differs(col, T):
     return scale_round_scalar(col, T, fused=True) != scale_round_scalar(col, T)
+
+
+def tables_by_tower(T, q_ref, rederive=True):
+    """NOT the reference: T's tables with the loop choice and the split point taken from the tower q_ref where the
+    reference takes them from q[0] (dcrtpoly-impl.h:1547).  What a kernel that branched or split on another tower
+    would compute; the sensitivity tests of tests/test_decrypt_cases.py need it.  rederive = False keeps the B
+    tables of q[0]'s split point, as a kernel does whose tables come from the caller and whose shift does not."""
+    W = copy.copy(T)
+    W.q_msb_hf = int(q_ref).bit_length() >> 1
+    W.branch = BT.decrypt_branch(len(T.q), int(q_ref), T.t)
+    W.split = bool(W.branch & 2)
+    if not rederive:
+        return W
+    XB = [(T.t * h) << W.q_msb_hf for h in BT.hat_inv(T.q)]
+    W.tQHatInvModqBDivqModt = [x // m % T.t for x, m in zip(XB, T.q)]
+    W.tQHatInvModqBDivqFrac = [float(x % m) / float(m) for x, m in zip(XB, T.q)]
+    return W
+
+
+def one_tower_scalar(v, q, t):
+    """one value of one_tower with Python integers and floats (mubintvecnat.cpp:420-435, ubintnat.h:536-540,
+    mubintvecnat.cpp:111-136; every word wraps mod 2^64 as NativeInteger's does) -> (output, the path it took):
+    path holds "upper" / "lower" (the side of q / 2), "wrapped" (q - MR(q - v) below zero), "reduced" (MR(v) >= q)
+    and the SwitchModulus branch "up" (t > q), "small" (q <= 2 t) or "down"."""
+    M = (1 << 64) - 1
+    mr = lambda y: int(float(t) * (float(y) / float(q)) + 0.5)  # noqa: E731
+    path = set()
+    if v > q >> 1:
+        path.add("upper")
+        if mr(q - v) > q:
+            path.add("wrapped")
+        r = (q - mr(q - v)) & M
+    else:
+        path.add("lower")
+        r = mr(v)
+        if r >= q:
+            path.add("reduced")
+            r %= q
+    if r > q >> 1:
+        r = (r + (t - q if t > q else t - q % t)) & M
+    if t > q:
+        path.add("up")
+    else:
+        path.add("small" if q <= 2 * t else "down")
+        if r >= t:
+            r %= t
+    return r, path
 
 
 def hps_case(O, c):

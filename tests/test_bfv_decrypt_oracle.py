@@ -12,6 +12,13 @@ definitions, on the very inputs tests/test_gpu_bfv_decrypt.py runs.
   (decrypt_ref.scale_round asserts it);
 * sensitivity: a fused multiply-add chain gives another output than the
   separately rounded one on planted coefficients (see test_fused_chain_differs).
+
+These are the cases the feature shipped with: towers of one size, small
+plaintext moduli, t < q / 2 on one tower.  The sweep beyond them (mixed chains,
+t up to 2^62, outputs equal to t, q <= 2 t and t > q, any 64-bit word into
+TimesQovert, every plan option of the decrypt call) is tests/decrypt_cases.py,
+with its coverage conditions in tests/test_decrypt_cases.py and its GPU parity
+in tests/test_gpu_fuzz_decrypt.py.
 """
 from fractions import Fraction
 
