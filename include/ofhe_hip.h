@@ -518,6 +518,83 @@ int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t handle, const uint64_t* c0, const uin
                            const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
                            void* stream);
 
+/* ---- BFV multiplication, HPSPOVERQLEVELED with dropped levels.  l is the index
+ *      of the last kept tower: Q_l = q_0 .. q_l and R_l = r_0 .. r_l have l + 1
+ *      towers each, Q is the full chain of size_q towers.  The caller chooses l
+ *      (FindLevelsToDrop, bfvrns-leveledshe.cpp:77-166); no call here does.
+ *      The floating-point contract above holds for every call unchanged.
+ *
+ * One level's handle, composed from handles the caller created and keeps alive
+ * (tables as bfvrns-cryptoparameters.cpp builds them for level l):
+ *   plan_q                 the full chain Q
+ *   plan_ql, plan_rl       Q_l and R_l; plan_qlrl their concatenation (:233-258)
+ *   ql_to_rl, rl_to_ql     converters with the true CRT tables of Q_l -> R_l and
+ *                          R_l -> Q_l (:156-188, :352-364, :390-439)
+ *   q_to_rl_neg            size_q sources -> l + 1 targets, created with
+ *                          mNegRlQHatInvModq(l) [size_q] (= q_i - R_l (Q/q_i)^-1 mod
+ *                          q_i, the full Q) and qInvModr [size_q][l + 1] (:501-523)
+ *   drop                   ScaleAndRound Q -> Q_l (QlQHatInvModqDivqModq(l) / Frac(l),
+ *                          :592-615): a handle with size_q = l + 1, size_p =
+ *                          size_q - l - 1, out_is_q = 1; NULL exactly when
+ *                          l == size_q - 1
+ *   scale_round            ScaleAndRound Q_l R_l -> Q_l (tQlSlHatInvModsDivsModq(l) /
+ *                          Frac(l), :558-586): size_q = size_p = l + 1, out_is_q = 1
+ *   ql_hat_modq            host [l + 1], QlHatModq(l)[i] = (Q / Q_l) mod q_i (:621-631)
+ * Every argument is checked before the device is touched: the contexts and the
+ * ring size, plan_ql / plan_rl against plan_qlrl, plan_ql as a prefix of plan_q,
+ * every handle's tower counts, ql_hat_modq[i] < q_i. */
+typedef struct ofhe_bfv_level_s* ofhe_bfv_level_t;
+int ofhe_hip_bfv_level_create(ofhe_ctx_t ctx, uint32_t l, ofhe_plan_t plan_q, ofhe_plan_t plan_ql, ofhe_plan_t plan_rl,
+                              ofhe_plan_t plan_qlrl, ofhe_bconv_t ql_to_rl, ofhe_bconv_t rl_to_ql,
+                              ofhe_bconv_t q_to_rl_neg, ofhe_scale_round_t drop, ofhe_scale_round_t scale_round,
+                              const uint64_t* ql_hat_modq, ofhe_bfv_level_t* handle);
+int ofhe_hip_bfv_level_destroy(ofhe_bfv_level_t handle);
+/* DCRTPolyImpl::ExpandCRTBasisQlHat (dcrtpoly-impl.h:1514-1534), with the
+ * addition that follows it in RelinearizeCore (bfvrns-leveledshe.cpp:889-896)
+ * when addend is not NULL:
+ *   out_i = x_i QlHatModq_i mod q_i (ModMulFastConstEq) [+ addend_i]   i <= l
+ *   out_i = addend_i, or 0 without an addend                           l < i < size_q
+ * x: [batch][l + 1][N]; addend, out: [batch][size_q][N]; any form, canonical
+ * words.  out may be addend itself; it must not overlap x (OFHE_ERR_ARG). */
+int ofhe_hip_expand_ql_hat(ofhe_bfv_level_t handle, const uint64_t* x, const uint64_t* addend, uint64_t* out,
+                           uint32_t batch, void* stream);
+/* ScaleAndRound to Q_l with the handle's scale_round tables
+ * (bfvrns-leveledshe.cpp:367-374; dcrtpoly-impl.h:1876-1955) and
+ * ExpandCRTBasisQlHat (:376-380; dcrtpoly-impl.h:1514-1534) in one launch:
+ * x [batch][2 (l + 1)][N] over Q_l R_l, coefficient form -> out
+ * [batch][size_q][N].  Word for word ofhe_hip_scale_and_round followed by
+ * ofhe_hip_expand_ql_hat. */
+int ofhe_hip_scale_round_expand_ql_hat(ofhe_bfv_level_t handle, const uint64_t* x, uint64_t* out, uint32_t batch,
+                                       void* stream);
+/* LeveledSHEBFVRNS::EvalMult, HPSPOVERQLEVELED at level l
+ * (bfvrns-leveledshe.cpp:235-274, 316-330, 367-382), and EvalSquare (:459-499)
+ * when d0 == c0 and d1 == c1.  c0, c1, d0, d1: [batch][size_q][N] evaluation
+ * form; out0..out2: [batch][size_q][N] coefficient form, as the reference leaves
+ * cvMult.  (c0, c1): INTT, ScaleAndRound Q -> Q_l when l < size_q - 1,
+ * ExpandCRTBasis Q_l -> Q_l R_l.  (d0, d1): INTT, FastExpandCRTBasisPloverQ
+ * (dcrtpoly-impl.h:1413-1466) from all size_q towers through q_to_rl_neg, the
+ * exact switch R_l -> Q_l, NTT.  Then the tensor product over Q_l R_l, INTT,
+ * ScaleAndRound to Q_l and ExpandCRTBasisQlHat.  At l == size_q - 1 the words
+ * are those of ofhe_hip_bfv_eval_mult with OFHE_BFV_HPSPOVERQ.  Scratch comes
+ * from the context's stream-ordered pool; no call synchronises. */
+int ofhe_hip_bfv_eval_mult_leveled(ofhe_bfv_level_t handle, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
+                                   const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
+                                   void* stream);
+/* LeveledSHEBFVRNS::RelinearizeCore, HPSPOVERQLEVELED at level l
+ * (bfvrns-leveledshe.cpp:845-899).  elements = 3: (c0, c1, c2); elements = 2:
+ * (c0, c1) and c2 must be NULL.  Inputs [batch][size_q][N], all in evaluation
+ * form (eval_form != 0) or all in coefficient form.  The last element is scaled
+ * to Q_l (:863-872), KeySwitchCore runs at l + 1 towers with the HYBRID engine
+ * ks (:878-879; keys laid out as for ofhe_hip_ks_core), ExpandCRTBasisQlHat
+ * lifts both results (:881-887), and out0 = c0 + ab0; out1 = c1 + ab1 with three
+ * elements, ab1 with two (:889-896).  out0, out1: [batch][size_q][N] evaluation
+ * form; they must not overlap the inputs.  ks must have been created for the
+ * chain Q of plan_q. */
+int ofhe_hip_bfv_relinearize_leveled(ofhe_bfv_level_t handle, ofhe_ks_t ks, uint32_t elements, int eval_form,
+                                     const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* key_b,
+                                     const uint64_t* key_a, uint64_t* out0, uint64_t* out1, uint32_t batch,
+                                     void* stream);
+
 /* BFV multiplication by the BEHZ technique: LeveledSHEBFVRNS::EvalMult's
  * `else` branches (bfvrns-leveledshe.cpp:275-297, 383-403) and the three
  * DCRTPolyImpl functions under them, HAVE_INT128 && NATIVEINT == 64 branches,
@@ -704,7 +781,8 @@ int ofhe_hip_bfv_decrypt_scale_round(ofhe_bfv_decrypt_t handle, const uint64_t* 
  * Coefficient-form elements are transformed first; one launch forms
  * b = c0 + c1 s (+ c2 s^2) towerwise with canonical results (s^2 in the
  * kernel); INTT through plan_q; the scale-round kernel.  The ciphertext must
- * have as many towers as the key (no HPSPOVERQLEVELED levels).  plan_q must
+ * have as many towers as the key (what ofhe_hip_bfv_eval_mult_leveled and
+ * ofhe_hip_bfv_relinearize_leveled return has: they lift to Q).  plan_q must
  * transform exactly the handle's towers at its N in its context.  Scratch
  * comes from the context's stream-ordered pool. */
 int ofhe_hip_bfv_decrypt(ofhe_bfv_decrypt_t handle, ofhe_plan_t plan_q, uint32_t elements, int eval_form,

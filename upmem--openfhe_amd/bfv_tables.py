@@ -4,7 +4,9 @@ integers and floats only (no device, no native library).
 A restatement of ``CryptoParametersBFVRNS::PrecomputeCRTTables``
 (pke/lib/scheme/bfvrns/bfvrns-cryptoparameters.cpp) for the full level: every
 table the calls of ``ofhe_hip.py`` (``BaseConverter``, ``ScaleRound``,
-``BfvMult``, ``Behz``, ``BfvDecrypt``) take.  The reference's line numbers are cited at each table.
+``BfvMult``, ``Behz``, ``BfvDecrypt``) take, and per level l for HPSPOVERQLEVELED
+(``LeveledTables``, what ``BfvLevel`` takes; ``levels_to_drop`` restates the
+reference's choice of l).  The reference's line numbers are cited at each table.
 
 The fractional tables are ``float(X mod s_i) / float(s_i)``: the reference's
 expression (two correctly rounded conversions and one IEEE division), not a
@@ -101,6 +103,95 @@ class BfvTables:
     @staticmethod
     def flat(rows) -> List[int]:
         return [v for row in rows for v in row]
+
+
+class LeveledTables:
+    """The tables of HPSPOVERQLEVELED at level l (the index of the last kept tower) for ciphertext
+    towers q, auxiliary towers r (len(r) == len(q)) and plaintext modulus t: Q_l = q[:l+1],
+    R_l = r[:l+1], Q the full chain.
+
+    * the true CRT tables of Q_l -> R_l and R_l -> Q_l with their alpha tables: QlHatInvModq(l),
+      QlHatModr(l) (:156-188), alphaQlModr(l) (:317-339), RlHatInvModr(l), RlHatModq(l) (:352-364,
+      :390-416), alphaRlModq(l) (:418-439), qInv / rInv (:270-273, :441-444)
+    * neg_rl_q_hat_inv_modq[i] = q_i - R_l (Q / q_i)^-1 mod q_i, i < size_q, with the FULL Q (:501-515)
+    * q_inv_modr[i][j] = q_i^-1 mod r_j, i < size_q, j <= l (:517-523)
+    * drop_table / drop_frac = QlQHatInvModqDivqModq(l) / Frac(l), ScaleAndRound Q -> Q_l (:592-615):
+      the summed towers are q[l+1:], the outputs q[:l+1]
+    * sr_table / sr_frac = tQlSlHatInvModsDivsModq(l) / Frac(l), ScaleAndRound Q_l R_l -> Q_l (:558-586)
+    * ql_hat_modq[i] = (Q / Q_l) mod q_i, i <= l (:621-631)
+
+    At l == len(q) - 1 the shared tables are BfvTables(q, r, t, HPSPOVERQ)'s and ``dropped`` is 0."""
+
+    def __init__(self, q: Sequence[int], r: Sequence[int], t: int, l: int):
+        self.q, self.r, self.t, self.l = [int(v) for v in q], [int(v) for v in r], int(t), int(l)
+        if len(self.r) != len(self.q):
+            raise ValueError("HPSPOVERQLEVELED needs as many auxiliary towers as ciphertext towers")
+        if not 0 <= self.l < len(self.q):
+            raise ValueError("l must be in [0, len(q) - 1]")
+        L = self.l + 1
+        self.ql, self.rl = self.q[:L], self.r[:L]
+        self.dropped = len(self.q) - L
+        Q, Ql, Rl = product(self.q), product(self.ql), product(self.rl)
+        self.Q, self.Ql, self.Rl = Q, Ql, Rl
+        self.q_hat_inv_modq = hat_inv(self.ql)
+        self.q_hat_modr = hat_mod(self.ql, self.rl)
+        self.r_hat_inv_modr = hat_inv(self.rl)
+        self.r_hat_modq = hat_mod(self.rl, self.ql)
+        self.alpha_q_modr = alpha_mod(self.ql, self.rl)
+        self.alpha_r_modq = alpha_mod(self.rl, self.ql)
+        self.q_inv = inv_doubles(self.ql)
+        self.r_inv = inv_doubles(self.rl)
+        self.neg_rl_q_hat_inv_modq = [qi - Rl * h % qi for qi, h in zip(self.q, hat_inv(self.q))]
+        self.q_inv_modr = [[pow(qi, -1, rj) for rj in self.rl] for qi in self.q]
+        self.drop_table, self.drop_frac = scale_round_tables(self.q[L:], self.ql, 1, Ql, Q)
+        self.sr_table, self.sr_frac = scale_round_tables(self.rl, self.ql, self.t, Ql, Ql * Rl)
+        self.ql_hat_modq = [Q // Ql % qi for qi in self.ql]
+        self.out_is_q = True
+
+
+def levels_to_drop(depth: int, size_q: int, dcrt_bits: float, n: int, t: int, sigma: float = 3.19,
+                   assurance: float = 36.0, digit_size: int = 0, hybrid: bool = True, num_per_part_q: int = 1,
+                   num_part_q: int = 1, threshold_parties: int = 1, gaussian_secret: bool = False,
+                   extended_encryption: bool = False, key_switch: bool = False) -> int:
+    """FindLevelsToDrop (bfvrns-leveledshe.cpp:77-166) with the quantities it reads from the crypto
+    parameters as plain arguments, in double precision and in the reference's order of operations:
+    depth = multiplicativeDepth, n = the ring dimension, t = the plaintext modulus, sigma / assurance
+    = GetDistributionParameter / GetAssuranceMeasure, digit_size = GetDigitSize (relinWindow),
+    hybrid = (GetKeySwitchTechnique() == HYBRID), num_per_part_q / num_part_q = GetNumPerPartQ /
+    GetNumPartQ.  The result is clamped to [0, size_q - 1]; the level is l = size_q - 1 - result."""
+    import math
+
+    p = float(t)
+    b_key = math.sqrt(threshold_parties) * sigma * math.sqrt(assurance) if gaussian_secret else float(threshold_parties)
+    w = math.pow(2, dcrt_bits) if digit_size == 0 else math.pow(2, digit_size)
+    b_err = sigma * math.sqrt(assurance)
+    delta = 2. * math.sqrt(n)
+    v_norm = (1. + delta * b_key) / 2. if extended_encryption else b_err * (1. + 2. * delta * b_key)
+
+    def noise_ks(logq_prev):
+        if hybrid:
+            return num_per_part_q * (num_part_q * delta * b_err + delta * b_key + 1.0) / 2
+        return delta * (math.floor(logq_prev / (math.log(2) * dcrt_bits)) + 1) * w * b_err
+
+    c1 = delta * delta * p * b_key
+
+    def c2(logq_prev):
+        return delta * delta * b_key * b_key / 2.0 + noise_ks(logq_prev)
+
+    def logq_bfv(logq_prev):
+        if depth > 0:
+            return math.log(4 * p) + (depth - 1) * math.log(c1) + math.log(c1 * v_norm + depth * c2(logq_prev))
+        return math.log(p * (4 * v_norm))
+
+    logq_prev = 6. * math.log(10)
+    logq = logq_bfv(logq_prev)
+    while math.fabs(logq - logq_prev) > math.log(1.001):
+        logq_prev = logq
+        logq = logq_bfv(logq_prev)
+    loge = logq / math.log(2) - 2 - math.log2(p)
+    log_extra = math.log2(noise_ks(logq)) if key_switch else math.log2(delta)
+    levels = math.floor((loge - 2 * depth - 16 - log_extra) / dcrt_bits)
+    return max(0, min(int(levels), size_q - 1))
 
 
 MTILDE = 1 << 16  # m_mtilde, the Montgomery modulus of the BEHZ base extension

@@ -15,13 +15,6 @@
 
 using namespace ofhe;
 
-struct ofhe_scale_round_s {
-    ofhe_ctx_t ctx = nullptr;
-    SrArgs args{};
-    u64* d_mem = nullptr;
-    u32 size_q = 0, size_p = 0, out_is_q = 0;
-};
-
 struct ofhe_bfv_mult_s {
     ofhe_ctx_t ctx = nullptr;
     u32 technique = 0;
@@ -39,6 +32,10 @@ int expand_check(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc) {
         return fail(OFHE_ERR_ARG, "base converter does not map plan_q's towers to plan_p's");
     return OFHE_OK;
 }
+
+}  // namespace
+
+namespace ofhe {
 
 // ExpandCRTBasis with resultFormat = EVALUATION, in the reference's order:
 // INTT of an evaluation-form input (1320-1323), exact switch Q -> P
@@ -73,7 +70,7 @@ int sr_run(ofhe_scale_round_t h, const u64* x, u64* out, u32 batch, hipStream_t 
     return post_launch();
 }
 
-}  // namespace
+}  // namespace ofhe
 
 int ofhe_hip_expand_crt_basis(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, int eval_form, const uint64_t* x,
                               uint64_t* out, uint32_t batch, void* stream) {

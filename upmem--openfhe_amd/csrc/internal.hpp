@@ -1,7 +1,8 @@
 // internal.hpp -- definitions shared by the translation units of the backend
 // (ofhe_hip.hip: context, plans, NTT, element-wise ops, base conversion;
 // keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching, rescaling;
-// bfv.hip: BFV multiplication (HPS family), ScaleAndRound; behz.hip: BFV
+// bfv.hip: BFV multiplication (HPS family), ScaleAndRound; bfv_leveled.hip:
+// HPSPOVERQLEVELED with dropped levels; behz.hip: BFV
 // multiplication (BEHZ); bfv_decrypt.hip: BFV decryption, TimesQovert; comm.hip:
 // multi-device collectives).
 // Not part of the C ABI.
@@ -204,6 +205,15 @@ int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t
 // output gap from A (a copy of b->args with the caller's strides).
 int switch_exact_run(ofhe_bconv_t b, const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);
 
+// ExpandCRTBasis with resultFormat = EVALUATION (bfv.hip): x [batch][Q][N] ->
+// out [batch][Q+P][N]; the handles are checked by the caller.
+int expand_run(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, int eval_form, const u64* x, u64* out, u32 batch,
+               hipStream_t s);
+
+// ScaleAndRound launch (k_scale_round, bfv.hip): x [batch][size_i + size_o][N] ->
+// out [batch][size_o][N].
+int sr_run(ofhe_scale_round_t h, const u64* x, u64* out, u32 batch, hipStream_t s);
+
 }  // namespace ofhe
 
 struct ofhe_ctx_s {
@@ -301,4 +311,11 @@ struct ofhe_bconv_s {
     // ofhe_hip_switch_crt_basis: host copies of the moduli; the exact switch's
     // tables (qInv, alphaQModp) are derived from them on the first exact call
     std::vector<ofhe::u64> hq, hp;
+};
+
+struct ofhe_scale_round_s {
+    ofhe_ctx_t ctx = nullptr;
+    ofhe::SrArgs args{};
+    ofhe::u64* d_mem = nullptr;
+    ofhe::u32 size_q = 0, size_p = 0, out_is_q = 0;
 };

@@ -25,6 +25,11 @@
 //                                FastBaseConvSK (dcrtpoly-impl.h:2050-2208,
 //                                2212-2271, 2309-2411, bfvrns-leveledshe.cpp:275-297,
 //                                383-403)
+//   BfvLevel / BfvLevelCache  <- HPSPOVERQLEVELED with dropped levels: EvalMult,
+//                                EvalSquare, RelinearizeCore, ExpandCRTBasisQlHat
+//                                (bfvrns-leveledshe.cpp:235-274, 367-382, 459-499,
+//                                845-899, dcrtpoly-impl.h:1514-1534) and
+//                                FindLevelsToDrop (bfvrns-leveledshe.cpp:77-166)
 //   KsCache / KeyCache        <- the per-parameter-set HYBRID tables
 //                                (rns-cryptoparameters.cpp:72-345) and the
 //                                evaluation keys kept resident on the device
@@ -36,6 +41,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <istream>
@@ -445,6 +451,7 @@ enum class Format { EVALUATION = 0, COEFFICIENT = 1 };
 // ModAdd/ModSub/ModMul with vector or scalar right-hand sides).
 // ---------------------------------------------------------------------------
 class BfvDecrypt;
+class BfvLevel;
 
 class DCRTPolyHip {
 public:
@@ -555,6 +562,11 @@ public:
     // TimesQovert (dcrtpoly-impl.h:1015-1031), in place, with the tInvModq and
     // negQModt of d's tables (defined after BfvDecrypt)
     inline void TimesQovert(const BfvDecrypt& d);
+
+    // ExpandCRTBasisQlHat (dcrtpoly-impl.h:1514-1534), in place: a polynomial
+    // over Q_l of the level becomes one over Q, towers i <= l times
+    // QlHatModq_i, the others zero; the format is kept (defined after BfvLevel)
+    inline void ExpandCRTBasisQlHat(const BfvLevel& level);
 
     // Times(const std::vector<NativeInteger>&): one scalar per tower (Shoup)
     DCRTPolyHip Times(const std::vector<uint64_t>& scalars) const {
@@ -1343,6 +1355,217 @@ private:
     static std::map<std::string, std::shared_ptr<const Key>>& map() {
         static std::map<std::string, std::shared_ptr<const Key>> m;
         return m;
+    }
+};
+
+// The tables of one level l of HPSPOVERQLEVELED as the reference's getters
+// return them (CryptoParametersBFVRNS, bfvrns-cryptoparameters.cpp:156-188,
+// 352-364, 501-523, 558-631), matrices flattened row-major.  l is the index of
+// the last kept tower.
+struct BfvLevelTables {
+    uint32_t l = 0;
+    std::vector<uint64_t> QlHatInvModq, QlHatModr;        // [l+1], [l+1][l+1]      GetQlHatInvModq(l), GetQlHatModr(l) as [i][j]
+    std::vector<uint64_t> RlHatInvModr, RlHatModq;        // [l+1], [l+1][l+1]      GetRlHatInvModr(l), GetRlHatModq(l) as [j][i]
+    std::vector<uint64_t> negRlQHatInvModq, qInvModr;     // [sizeQ], [sizeQ][l+1]  GetmNegRlQHatInvModq(l), GetqInvModr() cut to l+1 columns
+    std::vector<std::vector<uint64_t>> QlQHatInvModqDivqModq;    // [l+1][sizeQ-l]  GetQlQHatInvModqDivqModq(l)
+    std::vector<double> QlQHatInvModqDivqFrac;                   // [sizeQ-l-1]     GetQlQHatInvModqDivqFrac(l)
+    std::vector<std::vector<uint64_t>> tQlSlHatInvModsDivsModq;  // [l+1][l+2]      GettQlSlHatInvModsDivsModq(l)
+    std::vector<double> tQlSlHatInvModsDivsFrac;                 // [l+1]           GettQlSlHatInvModsDivsFrac(l)
+    std::vector<uint64_t> QlHatModq;                             // [l+1]           GetQlHatModq(l)
+};
+
+// FindLevelsToDrop (bfvrns-leveledshe.cpp:77-166) with the quantities it reads
+// from the crypto parameters as plain arguments, in the reference's order of
+// operations (doubles).  The kept level is l = sizeQ - 1 - the result.
+struct LevelsToDropParams {
+    double sigma = 3.19, assurance = 36;       // GetDistributionParameter, GetAssuranceMeasure
+    uint64_t plaintextModulus = 65537;
+    uint32_t ringDimension = 0, digitSize = 0;  // digitSize = relinWindow
+    bool hybrid = true;                         // GetKeySwitchTechnique() == HYBRID
+    uint32_t numPerPartQ = 1, numPartQ = 1, thresholdParties = 1;
+    bool gaussianSecret = false, extendedEncryption = false;
+    uint32_t sizeQ = 1;
+};
+inline uint32_t FindLevelsToDrop(uint32_t multiplicativeDepth, const LevelsToDropParams& cp, double dcrtBits,
+                                 bool keySwitch = false) {
+    const double sigma = cp.sigma, alpha = cp.assurance, p = static_cast<double>(cp.plaintextModulus);
+    const uint32_t n = cp.ringDimension, k = cp.numPerPartQ, numPartQ = cp.numPartQ;
+    const double Bkey = cp.gaussianSecret ? std::sqrt((double)cp.thresholdParties) * sigma * std::sqrt(alpha)
+                                          : (double)cp.thresholdParties;
+    const double w = cp.digitSize == 0 ? std::pow(2, dcrtBits) : std::pow(2, (double)cp.digitSize);
+    const double Berr = sigma * std::sqrt(alpha);
+    auto delta = [](uint32_t nn) -> double { return (2. * std::sqrt((double)nn)); };
+    auto Vnorm = [&](uint32_t nn) -> double {
+        if (cp.extendedEncryption) return (1. + delta(nn) * Bkey) / 2.;
+        return Berr * (1. + 2. * delta(nn) * Bkey);
+    };
+    auto noiseKS = [&](uint32_t nn, double logqPrev, double ww) -> double {
+        if (cp.hybrid) return k * (numPartQ * delta(nn) * Berr + delta(nn) * Bkey + 1.0) / 2;
+        return delta(nn) * (std::floor(logqPrev / (std::log(2) * dcrtBits)) + 1) * ww * Berr;
+    };
+    auto C1 = [&](uint32_t nn) -> double { return delta(nn) * delta(nn) * p * Bkey; };
+    auto C2 = [&](uint32_t nn, double logqPrev) -> double {
+        return delta(nn) * delta(nn) * Bkey * Bkey / 2.0 + noiseKS(nn, logqPrev, w);
+    };
+    auto logqBFV = [&](uint32_t nn, double logqPrev) -> double {
+        if (multiplicativeDepth > 0)
+            return std::log(4 * p) + (multiplicativeDepth - 1) * std::log(C1(nn)) +
+                   std::log(C1(nn) * Vnorm(nn) + multiplicativeDepth * C2(nn, logqPrev));
+        return std::log(p * (4 * (Vnorm(nn))));
+    };
+    double logqPrev = 6. * std::log(10);
+    double logq = logqBFV(n, logqPrev);
+    while (std::fabs(logq - logqPrev) > std::log(1.001)) {
+        logqPrev = logq;
+        logq = logqBFV(n, logqPrev);
+    }
+    const double loge = logq / std::log(2) - 2 - std::log2(p);
+    const double logExtra = keySwitch ? std::log2(noiseKS(n, logq, w)) : std::log2(delta(n));
+    int32_t levels = (int32_t)std::floor((loge - 2 * (double)multiplicativeDepth - 16 - logExtra) / dcrtBits);
+    if (levels < 0)
+        levels = 0;
+    else if (levels > static_cast<int32_t>(cp.sizeQ) - 1)
+        levels = (int32_t)cp.sizeQ - 1;
+    return (uint32_t)levels;
+}
+
+// One level of HPSPOVERQLEVELED: LeveledSHEBFVRNS::EvalMult / EvalSquare
+// (bfvrns-leveledshe.cpp:235-274, 316-330, 367-382, 459-499) and RelinearizeCore
+// (845-899) at the level l of the tables, for ciphertexts over Q with the
+// auxiliary basis R (as many towers as Q).  The caller chooses l
+// (FindLevelsToDrop) and asks BfvLevelCache for the level.
+class BfvLevel {
+public:
+    BfvLevel(std::shared_ptr<DCRTParams> Q, const std::shared_ptr<DCRTParams>& R, const BfvLevelTables& T)
+        : Q_(std::move(Q)), l_(T.l) {
+        const size_t sizeQ = Q_->Towers(), L = (size_t)T.l + 1;
+        if (L > sizeQ || R->Towers() < L) throw math_error("BfvLevel: l must be in [0, sizeQ - 1] and R hold l + 1 towers");
+        auto head = [&](const DCRTParams& P) {
+            return std::make_pair(std::vector<uint64_t>(P.Moduli().begin(), P.Moduli().begin() + L),
+                                  std::vector<uint64_t>(P.Roots().begin(), P.Roots().begin() + L));
+        };
+        auto ql = head(*Q_), rl = head(*R);
+        const uint32_t m = Q_->GetCyclotomicOrder();
+        const int dev = Q_->manager()->device();
+        Ql_ = std::make_shared<DCRTParams>(m, ql.first, ql.second, dev);
+        Rl_ = std::make_shared<DCRTParams>(m, rl.first, rl.second, dev);
+        ql.first.insert(ql.first.end(), rl.first.begin(), rl.first.end());
+        ql.second.insert(ql.second.end(), rl.second.begin(), rl.second.end());
+        QlRl_ = std::make_shared<DCRTParams>(m, ql.first, ql.second, dev);
+        if (T.QlHatModq.size() != L) throw math_error("BfvLevel: QlHatModq must have l + 1 entries");
+        ql_to_rl_.reset(new BaseConverter(*Ql_, *Rl_, T.QlHatInvModq, T.QlHatModr));
+        rl_to_ql_.reset(new BaseConverter(*Rl_, *Ql_, T.RlHatInvModr, T.RlHatModq));
+        neg_.reset(new BaseConverter(*Q_, *Rl_, T.negRlQHatInvModq, T.qInvModr));
+        if (L < sizeQ) {
+            DCRTParams dropped(m, std::vector<uint64_t>(Q_->Moduli().begin() + L, Q_->Moduli().end()),
+                               std::vector<uint64_t>(Q_->Roots().begin() + L, Q_->Roots().end()), dev);
+            drop_.reset(new ScaleAndRound(*Ql_, dropped, true, T.QlQHatInvModqDivqModq, T.QlQHatInvModqDivqFrac));
+        }
+        sr_.reset(new ScaleAndRound(*Ql_, *Rl_, true, T.tQlSlHatInvModsDivsModq, T.tQlSlHatInvModsDivsFrac));
+        check(ofhe_hip_bfv_level_create(Q_->manager()->ctx(), T.l, Q_->plan(), Ql_->plan(), Rl_->plan(), QlRl_->plan(),
+                                        ql_to_rl_->handle(), rl_to_ql_->handle(), neg_->handle(),
+                                        drop_ ? drop_->handle() : nullptr, sr_->handle(), T.QlHatModq.data(), &h_),
+              "BfvLevel");
+    }
+    ~BfvLevel() {
+        if (h_) ofhe_hip_bfv_level_destroy(h_);
+    }
+    BfvLevel(const BfvLevel&) = delete;
+    BfvLevel& operator=(const BfvLevel&) = delete;
+
+    // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
+    std::vector<DCRTPolyHip> EvalMult(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
+                                      const DCRTPolyHip& d1) const {
+        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
+            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
+                v->Batch() != c0.Batch())
+                throw math_error("BfvLevel::EvalMult: EVALUATION-form ciphertexts over Q of one batch expected");
+        std::vector<DCRTPolyHip> out;
+        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_bfv_eval_mult_leveled(h_, c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(),
+                                             out[1].data(), out[2].data(), c0.Batch(), nullptr),
+              "BfvLevel::EvalMult");
+        return out;
+    }
+    // EvalSquare (bfvrns-leveledshe.cpp:459-499): the values of EvalMult(c, c)
+    std::vector<DCRTPolyHip> EvalSquare(const DCRTPolyHip& c0, const DCRTPolyHip& c1) const {
+        return EvalMult(c0, c1, c0, c1);
+    }
+    // RelinearizeCore (bfvrns-leveledshe.cpp:845-899) of cv (3 or 2 elements over
+    // Q, all in one format) with the evaluation key (key_b, key_a): {cv[0], cv[1]}
+    // over Q in EVALUATION form.  ks is the HYBRID engine of Q (KsCache).
+    std::pair<DCRTPolyHip, DCRTPolyHip> Relinearize(const std::vector<const DCRTPolyHip*>& cv, const DCRTPolyHip& key_b,
+                                                    const DCRTPolyHip& key_a, const ofhe_ks_t ks) const {
+        if (cv.size() != 2 && cv.size() != 3) throw math_error("BfvLevel::Relinearize: 2 or 3 elements expected");
+        for (const DCRTPolyHip* v : cv)
+            if (!v || v->GetFormat() != cv[0]->GetFormat() || v->GetParams()->Moduli() != Q_->Moduli() ||
+                v->Batch() != cv[0]->Batch())
+                throw math_error("BfvLevel::Relinearize: elements over Q in one format and of one batch expected");
+        DCRTPolyHip o0(Q_, Format::EVALUATION, cv[0]->Batch(), DCRTPolyHip::Uninit{}),
+            o1(Q_, Format::EVALUATION, cv[0]->Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_bfv_relinearize_leveled(h_, ks, (uint32_t)cv.size(), cv[0]->GetFormat() == Format::EVALUATION,
+                                               cv[0]->data(), cv[1]->data(), cv.size() == 3 ? cv[2]->data() : nullptr,
+                                               key_b.data(), key_a.data(), o0.data(), o1.data(), cv[0]->Batch(),
+                                               nullptr),
+              "BfvLevel::Relinearize");
+        return {std::move(o0), std::move(o1)};
+    }
+    // ScaleAndRound to Q_l and ExpandCRTBasisQlHat in one launch: x over Q_l R_l
+    // (COEFFICIENT) -> Q
+    DCRTPolyHip ScaleAndRoundExpand(const DCRTPolyHip& x) const {
+        if (x.GetFormat() != Format::COEFFICIENT || x.GetParams()->Moduli() != QlRl_->Moduli())
+            throw math_error("BfvLevel::ScaleAndRoundExpand: a COEFFICIENT-form polynomial over Ql|Rl expected");
+        DCRTPolyHip out(Q_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_scale_round_expand_ql_hat(h_, x.data(), out.data(), x.Batch(), nullptr),
+              "BfvLevel::ScaleAndRoundExpand");
+        return out;
+    }
+    uint32_t Level() const { return l_; }
+    const std::shared_ptr<DCRTParams>& ParamsQ() const { return Q_; }
+    const std::shared_ptr<DCRTParams>& ParamsQl() const { return Ql_; }
+    const std::shared_ptr<DCRTParams>& ParamsRl() const { return Rl_; }
+    const std::shared_ptr<DCRTParams>& ParamsQlRl() const { return QlRl_; }
+    const BaseConverter& QlToRl() const { return *ql_to_rl_; }
+    const BaseConverter& RlToQl() const { return *rl_to_ql_; }
+    const BaseConverter& QToRlNeg() const { return *neg_; }
+    const ScaleAndRound* Drop() const { return drop_.get(); }  // null at l = sizeQ - 1
+    const ScaleAndRound& Scale() const { return *sr_; }
+    ofhe_bfv_level_t handle() const { return h_; }
+
+private:
+    std::shared_ptr<DCRTParams> Q_, Ql_, Rl_, QlRl_;
+    uint32_t l_;
+    std::unique_ptr<BaseConverter> ql_to_rl_, rl_to_ql_, neg_;
+    std::unique_ptr<ScaleAndRound> drop_, sr_;
+    ofhe_bfv_level_t h_ = nullptr;
+};
+
+inline void DCRTPolyHip::ExpandCRTBasisQlHat(const BfvLevel& level) {
+    if (p_->Moduli() != level.ParamsQl()->Moduli() || p_->LogN() != level.ParamsQl()->LogN())
+        throw math_error("ExpandCRTBasisQlHat: the polynomial is not over the level's Q_l");
+    DCRTPolyHip r(level.ParamsQ(), f_, batch_, Uninit{});
+    check(ofhe_hip_expand_ql_hat(level.handle(), data(), nullptr, r.data(), batch_, nullptr), "ExpandCRTBasisQlHat");
+    *this = std::move(r);
+}
+
+// BfvLevelCache: one BfvLevel per (device, N, Q, R, t-dependent tables' owner,
+// l) -- the reference precomputes every level's tables once per
+// CryptoParametersBFVRNS; `tables(l)` is called only on a miss.  owner
+// distinguishes parameter sets that share Q and R but not t.
+class BfvLevelCache {
+public:
+    template <class F>
+    static std::shared_ptr<BfvLevel> get(const std::shared_ptr<DCRTParams>& Q, const std::shared_ptr<DCRTParams>& R,
+                                         uint64_t owner, uint32_t l, F&& tables) {
+        static std::mutex mu;
+        static std::map<std::vector<uint64_t>, std::shared_ptr<BfvLevel>> cache;
+        std::vector<uint64_t> key{(uint64_t)Q->manager()->device(), Q->LogN(), owner, l, Q->Towers()};
+        key.insert(key.end(), Q->Moduli().begin(), Q->Moduli().end());
+        key.insert(key.end(), R->Moduli().begin(), R->Moduli().end());
+        std::lock_guard<std::mutex> lk(mu);
+        auto& e = cache[key];
+        if (!e) e = std::make_shared<BfvLevel>(Q, R, tables(l));
+        return e;
     }
 };
 

@@ -21,6 +21,10 @@ Host-side mirror of the reference's offload interface for the hot path:
   (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955) and ``LeveledSHEBFVRNS::EvalMult``
   for HPS / HPSPOVERQ (bfvrns-leveledshe.cpp:168-408); their tables come from
   ``bfv_tables.py``.
+* ``BfvLevel`` ~ ``LeveledSHEBFVRNS::EvalMult`` / ``EvalSquare`` / ``RelinearizeCore`` for HPSPOVERQLEVELED
+  with dropped levels (bfvrns-leveledshe.cpp:235-274, 367-382, 459-499, 845-899) and
+  ``DCRTPolyImpl::ExpandCRTBasisQlHat`` (dcrtpoly-impl.h:1514-1534); its tables are a
+  ``bfv_tables.LeveledTables``.
 * ``Behz`` ~ ``DCRTPolyImpl::FastBaseConvqToBskMontgomery`` / ``FastRNSFloorq`` / ``FastBaseConvSK``
   (dcrtpoly-impl.h:2050-2208, 2212-2271, 2309-2411) and ``LeveledSHEBFVRNS::EvalMult`` for BEHZ
   (bfvrns-leveledshe.cpp:275-297, 383-403); its tables are a ``bfv_tables.BehzTables``.
@@ -156,6 +160,15 @@ _SIGS = {
                                                 ctypes.POINTER(_vp)]),
     "ofhe_hip_bfv_mult_destroy": (ctypes.c_int, [_vp]),
     "ofhe_hip_bfv_eval_mult": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_level_create": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _u64p, ctypes.POINTER(_vp)]),
+    "ofhe_hip_bfv_level_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_expand_ql_hat": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_scale_round_expand_ql_hat": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bfv_eval_mult_leveled": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32,
+                                                      _vp]),
+    "ofhe_hip_bfv_relinearize_leveled": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_behz_create": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_uint32, _u64p,
                                             ctypes.c_uint64, _vp, ctypes.POINTER(_vp)]),
     "ofhe_hip_behz_destroy": (ctypes.c_int, [_vp]),
@@ -616,6 +629,72 @@ class BfvMult:
         """Inputs [batch][Q][N] evaluation form; outputs [batch][Q][N] coefficient form."""
         _check(lib().ofhe_hip_bfv_eval_mult(self._h, _vp(c0), _vp(c1), _vp(d0), _vp(d1), _vp(out0), _vp(out1),
                                             _vp(out2), int(batch), _vp(stream or None)))
+
+
+class BfvLevel:
+    """One level l of HPSPOVERQLEVELED (l = the index of the last kept tower), composed from the
+    caller's handles (kept alive by this object): plan_q over the full chain, plan_ql / plan_rl /
+    plan_qlrl over Q_l, R_l and both, ql_to_rl / rl_to_ql with the true CRT tables, q_to_rl_neg (all
+    size_q towers -> R_l with mNegRlQHatInvModq(l) / qInvModr), drop (ScaleRound Q -> Q_l, None at
+    l = size_q - 1), scale_round (Q_l R_l -> Q_l) and ql_hat_modq ((Q / Q_l) mod q_i, i <= l).
+    bfv_tables.LeveledTables holds every table."""
+
+    def __init__(self, ctx: Context, l: int, plan_q: NTTPlan, plan_ql: NTTPlan, plan_rl: NTTPlan, plan_qlrl: NTTPlan,
+                 ql_to_rl: BaseConverter, rl_to_ql: BaseConverter, q_to_rl_neg: BaseConverter,
+                 drop: Optional[ScaleRound], scale_round: ScaleRound, ql_hat_modq: Sequence[int]):
+        self._parts = (ctx, plan_q, plan_ql, plan_rl, plan_qlrl, ql_to_rl, rl_to_ql, q_to_rl_neg, drop, scale_round)
+        self.l = int(l)
+        if len(ql_hat_modq) != self.l + 1:
+            raise MathError("ql_hat_modq must have l + 1 entries")
+        h = _vp()
+        _check(lib().ofhe_hip_bfv_level_create(ctx.handle, self.l, plan_q.handle, plan_ql.handle, plan_rl.handle,
+                                               plan_qlrl.handle, ql_to_rl._h, rl_to_ql._h, q_to_rl_neg._h,
+                                               None if drop is None else drop._h, scale_round._h,
+                                               _arr(ql_hat_modq), ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(lib().ofhe_hip_bfv_level_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def expand_ql_hat(self, x: int, out: int, addend: int = 0, batch: int = 1, stream: int = 0) -> None:
+        """ExpandCRTBasisQlHat: x [batch][l + 1][N] -> out [batch][size_q][N], plus addend
+        [batch][size_q][N] when given (out may be the addend's buffer)."""
+        _check(lib().ofhe_hip_expand_ql_hat(self._h, _vp(x), _vp(addend or None), _vp(out), int(batch),
+                                            _vp(stream or None)))
+
+    def scale_round_expand(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        """ScaleAndRound Q_l R_l -> Q_l and ExpandCRTBasisQlHat in one launch: x [batch][2 (l + 1)][N]
+        coefficient form -> out [batch][size_q][N]."""
+        _check(lib().ofhe_hip_scale_round_expand_ql_hat(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+    def eval_mult(self, c0: int, c1: int, d0: int, d1: int, out0: int, out1: int, out2: int, batch: int = 1,
+                  stream: int = 0) -> None:
+        """Inputs [batch][size_q][N] evaluation form; outputs [batch][size_q][N] coefficient form."""
+        _check(lib().ofhe_hip_bfv_eval_mult_leveled(self._h, _vp(c0), _vp(c1), _vp(d0), _vp(d1), _vp(out0),
+                                                    _vp(out1), _vp(out2), int(batch), _vp(stream or None)))
+
+    def eval_square(self, c0: int, c1: int, out0: int, out1: int, out2: int, batch: int = 1, stream: int = 0) -> None:
+        """EvalSquare (bfvrns-leveledshe.cpp:459-499): the values of eval_mult(c, c)."""
+        self.eval_mult(c0, c1, c0, c1, out0, out1, out2, batch, stream)
+
+    def relinearize(self, ks: "KeySwitch", elements: Sequence[int], eval_form: bool, key_b: int, key_a: int,
+                    out0: int, out1: int, batch: int = 1, stream: int = 0) -> None:
+        """RelinearizeCore (bfvrns-leveledshe.cpp:845-899) of a 3- or 2-element ciphertext (device
+        pointers in `elements`, [batch][size_q][N], all in one form); outputs in evaluation form."""
+        if len(elements) not in (2, 3):
+            raise MathError("a ciphertext of 2 or 3 elements is needed")
+        c = [int(e) for e in elements] + [0]
+        _check(lib().ofhe_hip_bfv_relinearize_leveled(self._h, ks._h, len(elements), 1 if eval_form else 0, _vp(c[0]),
+                                                      _vp(c[1]), _vp(c[2] or None), _vp(key_b), _vp(key_a),
+                                                      _vp(out0), _vp(out1), int(batch), _vp(stream or None)))
 
 
 BEHZ_TWO_LAUNCHES, BEHZ_FUSED, BEHZ_AUTO = range(3)  # ofhe_hip_behz_floor_sk's `fused`
