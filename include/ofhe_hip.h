@@ -367,6 +367,75 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* di
                               const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint64_t t,
                               uint32_t batch, void* stream);
 
+/* ---- BSGS linear transform ("double hoisting") ----
+ * FHECKKSRNS::EvalLinearTransform (ckksrns-fhe.cpp:1484-1555), every level of
+ * EvalCoeffsToSlots / EvalSlotsToCoeffs (1636-1698 and the remainder blocks)
+ * and the same loops of ckksrns-schemeswitching.cpp:889-918, 994-1024: baby
+ * steps rotated into Ql|P, multiplied by plaintext diagonals and summed there,
+ * each giant step's sum switched down, rotated under the giant key and summed
+ * in Ql|P again, one final KeySwitchDown.  The three stage calls are the
+ * pieces the fused call runs; all outputs are canonical, nothing synchronises,
+ * and outputs must not alias inputs or each other. */
+/* KeySwitchHYBRID::KeySwitchExt (keyswitch-hybrid.cpp:231-256) on one element:
+ * c [batch][size_ql][N] -> out [batch][size_ql + size_p][N], c * (P mod q_i) on
+ * the Q towers and zero on the P towers. */
+int ofhe_hip_ks_ext(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* c, uint64_t* out, uint32_t batch,
+                    void* stream);
+/* EvalMultExt / EvalAddExtInPlace (ckksrns-fhe.cpp:2373-2396) over the inner
+ * loop of 1520-1526:  out_e[j] = sum_i x_e[i] * diag[j * nterm + i],  e = 0, 1,
+ * j < nsum, over Ql|P.  x0, x1: [nterm][batch][size_ql + size_p][N] with
+ * x_stride words between terms; diagonal d is (size_ql + size_p) towers of N in
+ * evaluation form at diag + d * diag_stride, shared by the batch entries;
+ * present (host bytes, [nsum * nterm], or NULL: all present) marks the
+ * diagonals that exist -- an absent one is skipped and never read;
+ * out0, out1: [nsum][batch][size_ql + size_p][N]. */
+int ofhe_hip_ks_mult_ext_sum(ofhe_ks_t ks, uint32_t size_ql, uint32_t nterm, const uint64_t* x0,
+                             const uint64_t* x1, uint64_t x_stride, const uint64_t* diag, uint64_t diag_stride,
+                             const uint8_t* present, uint32_t nsum, uint64_t* out0, uint64_t* out1,
+                             uint32_t batch, void* stream);
+/* Sum of EvalFastRotationExt(., index_j, digits_j, false)
+ * (ckksrns-leveledshe.cpp:402-457) over nset digit sets, each under its own key
+ * (EvalAddExtInPlace, ckksrns-fhe.cpp:1544-1545):
+ *   out_e[b] = sum_j sigma_kj(sum_d digits_j[b][d] * key_e_j[d])  (+ sum of addend1 on e = 1)
+ * digits: [nset][batch][beta][size_ql + size_p][N]; auto_index, key_b, key_a as
+ * for ofhe_hip_ks_fast_rotation_ext; addend1: [nadd][batch][size_ql + size_p][N]
+ * added to element 1 unrotated (the identity giant steps, 1528-1533), or NULL
+ * with nadd = 0; out0, out1: [batch][size_ql + size_p][N]. */
+int ofhe_hip_ks_fast_rotation_ext_sum(ofhe_ks_t ks, uint32_t size_ql, uint32_t nset, const uint64_t* digits,
+                                      const uint32_t* auto_index, const uint64_t* const* key_b,
+                                      const uint64_t* const* key_a, const uint64_t* addend1, uint32_t nadd,
+                                      uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream);
+/* One BSGS level.  Index arrays hold any odd values, taken mod 2N; an index
+ * = 1 mod 2N is the reference's no-rotation branch (KeySwitchExt for a baby
+ * step, 1521; KeySwitchDownFirstElement for a giant step, 1528-1533) and its key
+ * pointers are ignored.  Keys are host arrays of device pointers, laid out as
+ * for ofhe_hip_ks_fast_core_ext.  diag[j * nbaby + i] (device, diag_stride words
+ * apart, (size_ql + size_p) towers of N each) is giant step j's diagonal for
+ * baby step i; present: host bytes [ngiant * nbaby] or NULL (all present). */
+typedef struct ofhe_bsgs {
+    uint32_t nbaby, ngiant;
+    const uint32_t* baby_index;          /* [nbaby]  */
+    const uint32_t* giant_index;         /* [ngiant] */
+    const uint64_t* const* baby_key_b;   /* [nbaby]  */
+    const uint64_t* const* baby_key_a;
+    const uint64_t* const* giant_key_b;  /* [ngiant] */
+    const uint64_t* const* giant_key_a;
+    const uint64_t* diag;
+    uint64_t diag_stride;
+    const uint8_t* present;
+} ofhe_bsgs;
+/* With R_i = KeySwitchExt(ct) or EvalFastRotationExt(ct, baby_index[i], digits(c1), true),
+ * I_j = sum_{i present} R_i * diag[j * nbaby + i] (both elements, Ql|P):
+ *   identity giant j:  first += ModDown(I_j[0]);  outer[1] += I_j[1]
+ *   other giant j:     (m0, m1) = ModDown(I_j);   first += sigma_kj(m0);
+ *                      outer += EvalFastRotationExt((., m1), giant_index[j], digits(m1), false)
+ *   out0 = ModDown(outer[0]) + first,   out1 = ModDown(outer[1])
+ * ModDown as ofhe_hip_ks_mod_down with the same t, applied where the reference
+ * applies it (before the automorphism).  c0, c1, out0, out1: [batch][size_ql][N]. */
+int ofhe_hip_ks_bsgs_transform(ofhe_ks_t ks, uint32_t size_ql, const ofhe_bsgs* tr, const uint64_t* c0,
+                               const uint64_t* c1, uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch,
+                               void* stream);
+
 /* ---- element maps ---- */
 /* NativeVectorT::SwitchModulus (mubintvecnat.cpp:111-136) on n words:
  * values of modulus old_q re-centred to new_q, exactly as the reference. */

@@ -18,6 +18,7 @@
 
 #include "internal.hpp"
 #include "ks_kernels.hpp"
+#include "lt_kernels.hpp"
 
 using namespace ofhe;
 
@@ -92,7 +93,7 @@ static bool md_icol(const ModDownArgs& A) {
     return A.bcols && A.icol && !A.t_q && !A.tinv_p && A.plan_p == A.plan_q && A.plan_q->log_n == 17;
 }
 
-// ApproxModDown of nout = 1 or 2 inputs of `batch` entries each into out[k];
+// ApproxModDown of nout >= 1 inputs of `batch` entries each into out[k];
 // input k starts at x + k * batch * xstride (KeySwitchCore's ct1 follows its
 // ct0), so the P-part INTT, the base conversion and the column pass run once
 // over nout * batch polynomials; only the last pass, which writes the caller's
@@ -748,6 +749,286 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
         hipLaunchKernelGGL(k_add_automorphism, dim3(grid_for(per_rot), nr), dim3(256), 0, s, L->d_tow, md.w(), md1,
                            c0, out0 + r0 * per_rot, out1 + r0 * per_rot, I, per_rot, k->log_n, l);
         RCCHK(post_launch());
+    }
+    return OFHE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// BSGS linear transform (FHECKKSRNS::EvalLinearTransform, ckksrns-fhe.cpp:1484-1555;
+// the loops of EvalCoeffsToSlots / EvalSlotsToCoeffs, 1636-1698): lt_kernels.hpp
+// ---------------------------------------------------------------------------
+// [a, a + an) and [b, b + bn) (words) overlap
+static bool words_overlap(const u64* a, u64 an, const u64* b, u64 bn) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + 8 * bn && b0 < a0 + 8 * an;
+}
+
+static int ks_ext_impl(ofhe_ks_t k, KsLevel* L, const u64* c, u64* out, u32 batch, hipStream_t s) {
+    const u32 towers = L->size_ql + k->size_p;
+    const u64 nthreads = (u64)batch * towers << k->log_n;
+    hipLaunchKernelGGL(k_ks_ext, dim3((u32)((nthreads + 255) / 256)), dim3(256), 0, s, L->d_pmodq, c, out, nthreads,
+                       k->log_n, towers, L->size_ql);
+    return post_launch();
+}
+
+int ofhe_hip_ks_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, uint64_t* out, uint32_t batch, void* stream) {
+    if (!c || !out) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (batch == 0) return fail(OFHE_ERR_ARG, "batch must be >= 1");
+    RCCHK(ks_check(k, size_ql, batch));
+    const u64 N = 1ull << k->log_n;
+    if (words_overlap(c, (u64)batch * size_ql * N, out, (u64)batch * (size_ql + k->size_p) * N))
+        return fail(OFHE_ERR_ARG, "out must not alias c");
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    return ks_ext_impl(k, L, c, out, batch, pick(stream));
+}
+
+// k_lt_inner for the sums rows[0..nsum) (diagonal rows; sum g is written at
+// out + g * out_stride) over nterm terms: chunks of LT_SUM_CAP sums per launch
+// and of LT_TERM_CAP terms, the later term chunks adding into the stored sums.
+static int lt_inner_run(ofhe_ks_t k, KsLevel* L, u32 nterm, const u64* x0, const u64* x1, u64 x_stride,
+                        const u64* diag, u64 diag_stride, const uint8_t* present, const u32* rows, u32 nsum,
+                        u64* out0, u64* out1, u32 batch, hipStream_t s) {
+    const u32 towers = L->size_ql + k->size_p;
+    const u64 nthreads = (u64)batch * towers << k->log_n;
+    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
+    for (u32 g0 = 0; g0 < nsum; g0 += LT_SUM_CAP) {
+        const u32 ns = std::min(LT_SUM_CAP, nsum - g0);
+        for (u32 i0 = 0; i0 < nterm; i0 += LT_TERM_CAP) {
+            const u32 nt = std::min(LT_TERM_CAP, nterm - i0);
+            LtSums S{};
+            for (u32 j = 0; j < ns; j++) {
+                S.row[j] = rows[g0 + j];
+                u32 m = 0;
+                for (u32 i = 0; i < nt; i++)
+                    if (!present || present[(size_t)rows[g0 + j] * nterm + i0 + i]) m |= 1u << i;
+                S.mask[j] = m;
+            }
+            with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)nt, [&](auto NT_) {
+                hipLaunchKernelGGL((k_lt_inner<decltype(NT_)::value>), g, blk, 0, s, L->d_tow, x0 + i0 * x_stride,
+                                   x1 + i0 * x_stride, x_stride, diag + i0 * diag_stride, diag_stride,
+                                   (u64)nterm * diag_stride, S, ns, out0 + g0 * nthreads, out1 + g0 * nthreads,
+                                   nthreads, nthreads, k->log_n, towers, i0 ? 1u : 0u);
+            });
+            RCCHK(post_launch());
+        }
+    }
+    return OFHE_OK;
+}
+
+int ofhe_hip_ks_mult_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t nterm, const uint64_t* x0, const uint64_t* x1,
+                             uint64_t x_stride, const uint64_t* diag, uint64_t diag_stride, const uint8_t* present,
+                             uint32_t nsum, uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream) {
+    // the checks that need no engine first, then the engine, then those that need its dimensions
+    if (!x0 || !x1 || !diag || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (nterm == 0 || nsum == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nterm, nsum and batch must be >= 1");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    RCCHK(ks_check(k, size_ql, batch));
+    const u64 poly = (u64)(size_ql + k->size_p) << k->log_n, per = (u64)batch * poly;
+    if (diag_stride < poly) return fail(OFHE_ERR_ARG, "diag_stride smaller than one diagonal");
+    if (x_stride < per) return fail(OFHE_ERR_ARG, "x_stride smaller than one term");
+    const u64 xw = (u64)(nterm - 1) * x_stride + per, ow = (u64)nsum * per;
+    for (const u64* o : {out0, out1})
+        if (words_overlap(o, ow, x0, xw) || words_overlap(o, ow, x1, xw) ||
+            words_overlap(o, ow, diag, ((u64)nsum * nterm - 1) * diag_stride + poly))
+            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
+    if (words_overlap(out0, ow, out1, ow)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    std::vector<u32> rows(nsum);
+    for (u32 j = 0; j < nsum; j++) rows[j] = j;
+    return lt_inner_run(k, L, nterm, x0, x1, x_stride, diag, diag_stride, present, rows.data(), nsum, out0, out1,
+                        batch, pick(stream));
+}
+
+// k_lt_outer over nset digit sets (KS_ROT_CAP per launch, the later launches
+// adding into the stored result) plus nadd addends of element 1
+static int lt_outer_run(ofhe_ks_t k, KsLevel* L, const u64* digits, u32 nset, const u32* index,
+                        const u64* const* key_b, const u64* const* key_a, const u64* add1, u32 nadd, u64* out0,
+                        u64* out1, u32 batch, hipStream_t s) {
+    const u32 towers = L->size_ql + k->size_p;
+    const u64 poly = (u64)towers << k->log_n, nthreads = (u64)batch * poly;
+    const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
+    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
+    u32 j0 = 0;
+    do {
+        const u32 ns = std::min(KS_ROT_CAP, nset - j0);
+        LtRot R{};
+        for (u32 j = 0; j < ns; j++) {
+            R.kb[j] = key_b[j0 + j];
+            R.ka[j] = key_a[j0 + j];
+            R.k[j] = index[j0 + j];
+        }
+        const u64* dg = digits ? digits + (u64)j0 * batch * L->beta * poly : nullptr;
+        auto launch = [&](auto B_) {
+            hipLaunchKernelGGL((k_lt_outer<decltype(B_)::value>), g, blk, 0, s, L->d_tow, dg, R, ns, add1,
+                               j0 ? 0u : nadd, out0, out1, key_stride, nthreads, L->beta, k->log_n, towers, batch,
+                               j0 ? 1u : 0u);
+        };
+        if (!with_int<1, 2, 3, 4>((int)L->beta, launch)) launch(std::integral_constant<int, 0>{});
+        RCCHK(post_launch());
+        j0 += ns;
+    } while (j0 < nset);
+    return OFHE_OK;
+}
+
+int ofhe_hip_ks_fast_rotation_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t nset, const uint64_t* digits,
+                                      const uint32_t* auto_index, const uint64_t* const* key_b,
+                                      const uint64_t* const* key_a, const uint64_t* addend1, uint32_t nadd,
+                                      uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream) {
+    if (!digits || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (!auto_index || !key_b || !key_a) return fail(OFHE_ERR_ARG, "NULL index or key pointer array");
+    if (nset == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nset and batch must be >= 1");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    if ((addend1 == nullptr) != (nadd == 0)) return fail(OFHE_ERR_ARG, "addend1 and nadd must be given together");
+    for (u32 j = 0; j < nset; j++) {
+        if (!key_b[j] || !key_a[j]) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
+        if (auto_index[j] % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
+    }
+    RCCHK(ks_check(k, size_ql, batch));
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    const u64 per = (u64)batch * (size_ql + k->size_p) << k->log_n;
+    for (const u64* o : {(const u64*)out0, (const u64*)out1})
+        if (words_overlap(o, per, digits, (u64)nset * L->beta * per) ||
+            (addend1 && words_overlap(o, per, addend1, (u64)nadd * per)))
+            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
+    if (words_overlap(out0, per, out1, per)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    return lt_outer_run(k, L, digits, nset, auto_index, key_b, key_a, addend1, nadd, out0, out1, batch,
+                        pick(stream));
+}
+
+int ofhe_hip_ks_bsgs_transform(ofhe_ks_t k, uint32_t size_ql, const ofhe_bsgs* tr, const uint64_t* c0,
+                               const uint64_t* c1, uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch,
+                               void* stream) {
+    // the checks that need no engine first, then the engine, then those that need its dimensions
+    if (!tr || !c0 || !c1 || !out0 || !out1 || !tr->diag) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (!tr->baby_index || !tr->giant_index || !tr->baby_key_b || !tr->baby_key_a || !tr->giant_key_b ||
+        !tr->giant_key_a)
+        return fail(OFHE_ERR_ARG, "NULL index or key pointer array");
+    const u32 nb = tr->nbaby, ng = tr->ngiant;
+    if (nb == 0 || ng == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nbaby, ngiant and batch must be >= 1");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    for (u32 i = 0; i < nb + ng; i++)
+        if ((i < nb ? tr->baby_index[i] : tr->giant_index[i - nb]) % 2 == 0)
+            return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
+    RCCHK(ks_check(k, size_ql, batch));
+    const u32 l = size_ql, P = k->size_p;
+    const u64 N = 1ull << k->log_n, poly = (u64)(l + P) * N, per = (u64)batch * poly, qper = (u64)batch * l * N;
+    if (tr->diag_stride < poly) return fail(OFHE_ERR_ARG, "diag_stride smaller than one diagonal");
+    const u32 m2 = (u32)(2 * N - 1);
+    auto is_id = [&](u32 idx) { return (idx & m2) == 1; };
+    for (u32 i = 0; i < nb + ng; i++) {
+        const bool baby = i < nb;
+        const u32 r = baby ? i : i - nb, idx = baby ? tr->baby_index[r] : tr->giant_index[r];
+        const u64* kb = baby ? tr->baby_key_b[r] : tr->giant_key_b[r];
+        const u64* ka = baby ? tr->baby_key_a[r] : tr->giant_key_a[r];
+        if (!is_id(idx) && (!kb || !ka)) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
+    }
+    const u64 dw = ((u64)nb * ng - 1) * tr->diag_stride + poly;
+    for (const u64* o : {(const u64*)out0, (const u64*)out1})
+        if (words_overlap(o, qper, c0, qper) || words_overlap(o, qper, c1, qper) ||
+            words_overlap(o, qper, tr->diag, dw))
+            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
+    if (words_overlap(out0, qper, out1, qper)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    hipStream_t s = pick(stream);
+    ModDownArgs A;
+    RCCHK(ks_md_args(k, L, t, &A));
+
+    // giant steps: the non-identity ones first, then the identity ones
+    std::vector<u32> rows, gidx;
+    std::vector<const u64*> gkb, gka;
+    for (int pass = 0; pass < 2; pass++)
+        for (u32 j = 0; j < ng; j++)
+            if (is_id(tr->giant_index[j]) == (pass == 1)) {
+                rows.push_back(j);
+                if (pass == 0) {
+                    gidx.push_back(tr->giant_index[j]);
+                    gkb.push_back(tr->giant_key_b[j]);
+                    gka.push_back(tr->giant_key_a[j]);
+                }
+            }
+    const u32 nrot = (u32)gidx.size(), nid = ng - nrot;
+
+    // 1-2. R_i, both elements, over Ql|P: [nbaby][batch][l+P][N] each
+    Scratch rb, dg;
+    RCCHK(rb.alloc((size_t)2 * nb * per * 8, s, k->ctx));
+    u64* r0 = rb.w();
+    u64* r1 = r0 + (u64)nb * per;
+    bool any_rot = false;
+    for (u32 i = 0; i < nb; i++) any_rot |= !is_id(tr->baby_index[i]);
+    if (any_rot) {
+        RCCHK(dg.alloc((size_t)L->beta * per * 8, s, k->ctx));
+        RCCHK(ks_precompute_impl(k, L, l, c1, dg.w(), batch, s, true));
+    }
+    for (u32 i = 0; i < nb;) {
+        if (is_id(tr->baby_index[i])) {  // KeySwitchExt(ct, true), ckksrns-fhe.cpp:1521
+            RCCHK(ks_ext_impl(k, L, c0, r0 + i * per, batch, s));
+            RCCHK(ks_ext_impl(k, L, c1, r1 + i * per, batch, s));
+            i++;
+            continue;
+        }
+        u32 n = 0, kinv[KS_ROT_CAP];  // a run of rotations: EvalFastRotationExt(ct, ., digits, true), 1513-1515
+        for (; i + n < nb && n < KS_ROT_CAP && !is_id(tr->baby_index[i + n]); n++)
+            kinv[n] = inv_odd32(tr->baby_index[i + n]);
+        RCCHK(ks_inner_rot(k, L, l, dg.w(), c0, n, kinv, tr->baby_key_b + i, tr->baby_key_a + i, r0 + i * per,
+                           r1 + i * per, per, batch, s));
+        i += n;
+    }
+
+    // 3. I_j: element 0 then element 1 of the rotated giants (one ModDown batch),
+    // the identity giants' second elements, and their first elements behind the
+    // two outer sums, whose ModDown they share (step 7)
+    Scratch ib, ou;
+    RCCHK(ib.alloc((size_t)(2 * nrot + nid) * per * 8, s, k->ctx));
+    RCCHK(ou.alloc((size_t)(2 + nid) * per * 8, s, k->ctx));
+    u64* i0r = ib.w();
+    u64* i1r = i0r + (u64)nrot * per;
+    u64* i1d = i1r + (u64)nrot * per;
+    u64* i0d = ou.w() + 2 * per;
+    if (nrot)
+        RCCHK(lt_inner_run(k, L, nb, r0, r1, per, tr->diag, tr->diag_stride, tr->present, rows.data(), nrot, i0r,
+                           i1r, batch, s));
+    if (nid)
+        RCCHK(lt_inner_run(k, L, nb, r0, r1, per, tr->diag, tr->diag_stride, tr->present, rows.data() + nrot, nid,
+                           i0d, i1d, batch, s));
+
+    // 4. KeySwitchDown of every rotated giant's sum, both elements, as one batch (1536)
+    Scratch md, dg2;
+    RCCHK(md.alloc((size_t)(2 * nrot + nid) * qper * 8, s, k->ctx));
+    u64* md0 = md.w();
+    u64* md1 = md0 + (u64)nrot * qper;
+    u64* mdid = md1 + (u64)nrot * qper;
+    if (nrot) {
+        u64* const outs[2] = {md0, md1};
+        RCCHK(mod_down_run(A, i0r, poly, outs, 2, (u64)l * N, nrot * batch, s));
+    }
+
+    // 5-6. the rotated giants' second elements decomposed as one batch (1544),
+    // key-switched, rotated and summed (1545); outer1 follows outer0
+    if (nrot) {
+        RCCHK(dg2.alloc((size_t)nrot * L->beta * per * 8, s, k->ctx));
+        RCCHK(ks_precompute_impl(k, L, l, md1, dg2.w(), nrot * batch, s, true));
+    }
+    RCCHK(lt_outer_run(k, L, nrot ? dg2.w() : nullptr, nrot, gidx.data(), gkb.data(), gka.data(), nid ? i1d : nullptr,
+                       nid, ou.w(), ou.w() + per, batch, s));
+
+    // 7-8. the last KeySwitchDown (1549) together with KeySwitchDownFirstElement
+    // of the identity giants (1529), whose result is not needed earlier: one set
+    // of launches over 2 + nid polynomials per entry; then += first (1551)
+    std::vector<u64*> outs{out0, out1};
+    for (u32 j = 0; j < nid; j++) outs.push_back(mdid + (u64)j * qper);
+    RCCHK(mod_down_run(A, ou.w(), poly, outs.data(), 2 + nid, (u64)l * N, batch, s));
+    for (u32 j0 = 0, first = 1; first || j0 < nrot; first = 0) {
+        const u32 ns = std::min(KS_ROT_CAP, nrot - j0);
+        LtIdx I{};
+        for (u32 j = 0; j < ns; j++) I.k[j] = gidx[j0 + j];
+        hipLaunchKernelGGL(k_lt_first, dim3((u32)((qper + 255) / 256)), dim3(256), 0, s, L->d_tow, out0,
+                           md0 + (u64)j0 * qper, I, ns, mdid, first ? nid : 0u, out0, qper, k->log_n, l);
+        RCCHK(post_launch());
+        j0 += ns;
     }
     return OFHE_OK;
 }

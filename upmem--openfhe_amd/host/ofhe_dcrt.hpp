@@ -1254,9 +1254,104 @@ public:
         });
     }
 
+    // ---- BSGS linear transform (FHECKKSRNS::EvalLinearTransform, ckksrns-fhe.cpp:1484-1555) ----
+    // Polynomials that the C ABI takes as [count][batch][towers][N] are one
+    // DCRTPolyHip whose Batch() is count * batch, count-major.
+
+    // KeySwitchHYBRID::KeySwitchExt (keyswitch-hybrid.cpp:231-256) on one
+    // element: c over Ql -> c * PModq on the Q towers of paramsQlP, zero on P.
+    DCRTPolyHip KeySwitchExt(const DCRTPolyHip& c, const std::shared_ptr<DCRTParams>& paramsQlP) const {
+        if (c.GetFormat() != Format::EVALUATION) throw math_error("KeySwitchExt: EVALUATION form expected");
+        const uint32_t l = (uint32_t)c.GetParams()->Towers();
+        ext_params("KeySwitchExt", paramsQlP, l);
+        DCRTPolyHip out(paramsQlP, Format::EVALUATION, c.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_ks_ext(h_, l, c.data(), out.data(), c.Batch(), nullptr), "KeySwitchExt");
+        return out;
+    }
+
+    // EvalMultExt / EvalAddExtInPlace over the inner loop of 1520-1526:
+    // out_e[j] = sum_i x_e[i] * diag[j * nterm + i].  x0, x1: nterm * batch
+    // polynomials over Ql|P; diag: nsum * nterm; present: empty (all) or one
+    // byte per diagonal.  Returns (out0, out1) with nsum * batch polynomials each.
+    std::pair<DCRTPolyHip, DCRTPolyHip> MultExtSum(const DCRTPolyHip& x0, const DCRTPolyHip& x1, uint32_t nterm,
+                                                   const DCRTPolyHip& diag, const std::vector<uint8_t>& present,
+                                                   uint32_t nsum) const {
+        const auto& op = x0.GetParams();
+        if (x0.GetFormat() != Format::EVALUATION || x1.GetFormat() != Format::EVALUATION ||
+            diag.GetFormat() != Format::EVALUATION)
+            throw math_error("MultExtSum: EVALUATION form expected");
+        if (op->Towers() <= sizeP_ || x1.GetParams()->Moduli() != op->Moduli() ||
+            diag.GetParams()->Moduli() != op->Moduli())
+            throw math_error("MultExtSum: the terms and the diagonals must be over one Ql|P basis");
+        if (!nterm || !nsum || x0.Batch() % nterm || x1.Batch() != x0.Batch() || diag.Batch() != (size_t)nsum * nterm)
+            throw math_error("MultExtSum: nterm * batch terms and nsum * nterm diagonals required");
+        if (!present.empty() && present.size() != (size_t)nsum * nterm)
+            throw math_error("MultExtSum: one presence byte per diagonal required");
+        const uint32_t batch = x0.Batch() / nterm, l = (uint32_t)(op->Towers() - sizeP_);
+        const uint64_t poly = (uint64_t)op->Towers() * op->GetRingDimension();
+        DCRTPolyHip o0(op, Format::EVALUATION, nsum * batch, DCRTPolyHip::Uninit{}),
+            o1(op, Format::EVALUATION, nsum * batch, DCRTPolyHip::Uninit{});
+        check(ofhe_hip_ks_mult_ext_sum(h_, l, nterm, x0.data(), x1.data(), batch * poly, diag.data(), poly,
+                                       present.empty() ? nullptr : present.data(), nsum, o0.data(), o1.data(), batch,
+                                       nullptr),
+              "MultExtSum");
+        return {std::move(o0), std::move(o1)};
+    }
+
+    // Sum over the digit sets of EvalFastRotationExt(., autoIndex[j], digits_j, false)
+    // under keys[j] (1544-1545).  digits: FastRotationPrecompute of nset * batch
+    // polynomials, set-major; addend1: nadd * batch polynomials over Ql|P added
+    // to the second element, or nullptr.
+    std::pair<DCRTPolyHip, DCRTPolyHip> FastRotationExtSum(const HoistedDigits& digits,
+                                                           const std::vector<uint32_t>& autoIndex,
+                                                           const std::vector<RotationKey>& keys,
+                                                           const DCRTPolyHip* addend1,
+                                                           const std::shared_ptr<DCRTParams>& paramsQlP) const {
+        rot_check("FastRotationExtSum", nullptr, digits, autoIndex, keys);
+        ext_params("FastRotationExtSum", paramsQlP, digits.size_ql);
+        const uint32_t nset = (uint32_t)autoIndex.size();
+        if (digits.batch % nset) throw math_error("FastRotationExtSum: the digits must hold nset * batch polynomials");
+        const uint32_t batch = digits.batch / nset;
+        if (addend1 && (addend1->GetFormat() != Format::EVALUATION || addend1->Batch() % batch ||
+                        addend1->GetParams()->Moduli() != paramsQlP->Moduli()))
+            throw math_error("FastRotationExtSum: addend1 must be nadd * batch EVALUATION polynomials over Ql|P");
+        KeyPtrs k;
+        for (const auto& key : keys) {
+            k.b.push_back(key.first->data());
+            k.a.push_back(key.second->data());
+        }
+        DCRTPolyHip o0(paramsQlP, Format::EVALUATION, batch, DCRTPolyHip::Uninit{}),
+            o1(paramsQlP, Format::EVALUATION, batch, DCRTPolyHip::Uninit{});
+        check(ofhe_hip_ks_fast_rotation_ext_sum(h_, digits.size_ql, nset, digits.buf.get(), autoIndex.data(),
+                                                k.b.data(), k.a.data(), addend1 ? addend1->data() : nullptr,
+                                                addend1 ? addend1->Batch() / batch : 0, o0.data(), o1.data(), batch,
+                                                nullptr),
+              "FastRotationExtSum");
+        return {std::move(o0), std::move(o1)};
+    }
+
+    // One BSGS level: indices, key ids and presence.  An index = 1 mod 2N is
+    // the reference's no-rotation branch and its key id is ignored.
+    struct BsgsPlan {
+        std::vector<uint32_t> babyIndex, giantIndex;  // automorphism indices (FindAutomorphismIndex2nComplex)
+        std::vector<std::string> babyKey, giantKey;   // KeyCache ids of the rotation keys
+        std::vector<uint8_t> present;                 // [ngiant * nbaby], empty: every diagonal exists
+    };
+    // (c0, c1) over Ql -> the transform's (c0', c1') over Ql; diag: ngiant *
+    // nbaby polynomials over Ql|P, diag[j * nbaby + i] for giant j and baby i,
+    // uploaded once at setup.  Defined after KeyCache.
+    std::pair<DCRTPolyHip, DCRTPolyHip> LinearTransform(const DCRTPolyHip& c0, const DCRTPolyHip& c1,
+                                                        const BsgsPlan& plan, const DCRTPolyHip& diag,
+                                                        uint64_t t = 0) const;
+
     ofhe_ks_t handle() const { return h_; }
 
 private:
+    void ext_params(const char* op, const std::shared_ptr<DCRTParams>& paramsQlP, size_t l) const {
+        if (l > sizeQ_) throw math_error(std::string(op) + ": ciphertext has more towers than Q");
+        if (!paramsQlP || paramsQlP->Towers() != l + sizeP_)
+            throw math_error(std::string(op) + ": paramsQlP must have the level's towers plus P");
+    }
     struct KeyPtrs {
         std::vector<const uint64_t*> b, a;
     };
@@ -1357,6 +1452,64 @@ private:
         return m;
     }
 };
+
+inline std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchHybrid::LinearTransform(const DCRTPolyHip& c0,
+                                                                            const DCRTPolyHip& c1,
+                                                                            const BsgsPlan& plan,
+                                                                            const DCRTPolyHip& diag,
+                                                                            uint64_t t) const {
+    if (c0.GetFormat() != Format::EVALUATION || c1.GetFormat() != Format::EVALUATION ||
+        diag.GetFormat() != Format::EVALUATION)
+        throw math_error("LinearTransform: EVALUATION form expected");
+    const size_t l = c0.GetParams()->Towers(), nb = plan.babyIndex.size(), ng = plan.giantIndex.size();
+    if (l > sizeQ_ || c1.GetParams()->Moduli() != c0.GetParams()->Moduli() || c1.Batch() != c0.Batch())
+        throw math_error("LinearTransform: c0 and c1 must be one ciphertext over Ql");
+    if (!nb || !ng || plan.babyKey.size() != nb || plan.giantKey.size() != ng)
+        throw math_error("LinearTransform: one key id per baby and giant step required");
+    if (diag.GetParams()->Towers() != l + sizeP_ || diag.Batch() != nb * ng)
+        throw math_error("LinearTransform: ngiant * nbaby diagonals over Ql|P required");
+    if (!plan.present.empty() && plan.present.size() != nb * ng)
+        throw math_error("LinearTransform: one presence byte per diagonal required");
+    const uint64_t two_n = 2 * (uint64_t)c0.GetParams()->GetRingDimension();
+    std::vector<std::shared_ptr<const KeyCache::Key>> hold;  // resident keys stay alive through the call
+    std::vector<const uint64_t*> kb[2], ka[2];
+    for (int g = 0; g < 2; g++) {
+        const auto& idx = g ? plan.giantIndex : plan.babyIndex;
+        const auto& ids = g ? plan.giantKey : plan.babyKey;
+        for (size_t i = 0; i < idx.size(); i++) {
+            if (idx[i] % two_n == 1) {
+                kb[g].push_back(nullptr);
+                ka[g].push_back(nullptr);
+                continue;
+            }
+            auto key = KeyCache::get(ids[i]);
+            if (key->b.Batch() != numPartQ_ || key->a.Batch() != numPartQ_ ||
+                key->b.GetParams()->Towers() != sizeQ_ + sizeP_ || key->a.GetParams()->Towers() != sizeQ_ + sizeP_)
+                throw math_error("LinearTransform: evaluation key must be numPartQ polynomials over Q|P");
+            kb[g].push_back(key->b.data());
+            ka[g].push_back(key->a.data());
+            hold.push_back(std::move(key));
+        }
+    }
+    ofhe_bsgs tr{};
+    tr.nbaby = (uint32_t)nb;
+    tr.ngiant = (uint32_t)ng;
+    tr.baby_index = plan.babyIndex.data();
+    tr.giant_index = plan.giantIndex.data();
+    tr.baby_key_b = kb[0].data();
+    tr.baby_key_a = ka[0].data();
+    tr.giant_key_b = kb[1].data();
+    tr.giant_key_a = ka[1].data();
+    tr.diag = diag.data();
+    tr.diag_stride = (uint64_t)(l + sizeP_) * c0.GetParams()->GetRingDimension();
+    tr.present = plan.present.empty() ? nullptr : plan.present.data();
+    DCRTPolyHip o0(c0.GetParams(), Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{}),
+        o1(c0.GetParams(), Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{});
+    check(ofhe_hip_ks_bsgs_transform(h_, (uint32_t)l, &tr, c0.data(), c1.data(), o0.data(), o1.data(), t, c0.Batch(),
+                                     nullptr),
+          "LinearTransform");
+    return {std::move(o0), std::move(o1)};
+}
 
 // The tables of one level l of HPSPOVERQLEVELED as the reference's getters
 // return them (CryptoParametersBFVRNS, bfvrns-cryptoparameters.cpp:156-188,

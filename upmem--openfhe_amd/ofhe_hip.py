@@ -15,7 +15,9 @@ Host-side mirror of the reference's offload interface for the hot path:
   with the tables of ``CryptoParametersRNS::PrecomputeCRTTables``; its
   ``fast_rotation`` / ``fast_rotation_ext`` ~ ``EvalFastRotation``
   (base-leveledshe.cpp:471-513) / ``EvalFastRotationExt``
-  (ckksrns-leveledshe.cpp:402-457) for many keys over one digit set.
+  (ckksrns-leveledshe.cpp:402-457) for many keys over one digit set; its
+  ``bsgs_transform`` (stages ``ext``, ``mult_ext_sum``, ``fast_rotation_ext_sum``) ~ one
+  BSGS level of ``FHECKKSRNS::EvalLinearTransform`` (ckksrns-fhe.cpp:1484-1555).
 * ``BaseConverter.switch_exact`` / ``expand_crt_basis`` / ``ScaleRound`` / ``BfvMult`` ~
   ``DCRTPolyImpl::SwitchCRTBasis`` / ``ExpandCRTBasis`` / ``ScaleAndRound``
   (dcrtpoly-impl.h:1178-1230, 1311-1358, 1876-1955) and ``LeveledSHEBFVRNS::EvalMult``
@@ -62,6 +64,16 @@ class MathError(RuntimeError):
 _lib: Optional[ctypes.CDLL] = None
 
 # name -> (restype, argtypes)
+class Bsgs(ctypes.Structure):
+    """ofhe_bsgs: one BSGS level of ofhe_hip_ks_bsgs_transform."""
+    _fields_ = [("nbaby", ctypes.c_uint32), ("ngiant", ctypes.c_uint32),
+                ("baby_index", ctypes.POINTER(ctypes.c_uint32)), ("giant_index", ctypes.POINTER(ctypes.c_uint32)),
+                ("baby_key_b", ctypes.POINTER(ctypes.c_void_p)), ("baby_key_a", ctypes.POINTER(ctypes.c_void_p)),
+                ("giant_key_b", ctypes.POINTER(ctypes.c_void_p)), ("giant_key_a", ctypes.POINTER(ctypes.c_void_p)),
+                ("diag", ctypes.c_void_p), ("diag_stride", ctypes.c_uint64),
+                ("present", ctypes.POINTER(ctypes.c_uint8))]
+
+
 _SIGS = {
     "ofhe_hip_last_error": (ctypes.c_char_p, []),
     "ofhe_hip_version": (ctypes.c_char_p, []),
@@ -138,6 +150,16 @@ _SIGS = {
                                                  ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_vp),
                                                  ctypes.POINTER(_vp), _vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
                                                  _vp]),
+    "ofhe_hip_ks_ext": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_mult_ext_sum": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64,
+                                                _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
+                                                ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_fast_rotation_ext_sum": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                                         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_vp),
+                                                         ctypes.POINTER(_vp), _vp, ctypes.c_uint32, _vp, _vp,
+                                                         ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_bsgs_transform": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(Bsgs), _vp, _vp, _vp, _vp,
+                                                  ctypes.c_uint64, ctypes.c_uint32, _vp]),
     "ofhe_hip_switch_modulus": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                _vp]),
     "ofhe_hip_automorphism": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
@@ -945,6 +967,56 @@ class KeySwitch:
         n, idx, kb, ka = self._rot_args(auto_indices, key_b_ptrs, key_a_ptrs)
         _check(lib().ofhe_hip_ks_fast_rotation(self._h, int(size_ql), _vp(digits), _vp(c0 or None), n, idx, kb, ka,
                                                _vp(out0), _vp(out1), int(t), int(batch), _vp(stream or None)))
+
+    @staticmethod
+    def _present(present, count):
+        """Host byte array of the diagonals that exist; None stays NULL (all present)."""
+        if present is None:
+            return None
+        if len(present) != count:
+            raise MathError("present needs one entry per diagonal")
+        return (ctypes.c_uint8 * count)(*[1 if v else 0 for v in present])
+
+    def ext(self, size_ql: int, c: int, out: int, batch: int = 1, stream: int = 0) -> None:
+        """KeySwitchHYBRID::KeySwitchExt (keyswitch-hybrid.cpp:231-256) on one element:
+        c [batch][size_ql][N] -> out [batch][size_ql + size_p][N]."""
+        _check(lib().ofhe_hip_ks_ext(self._h, int(size_ql), _vp(c or None), _vp(out or None), int(batch),
+                                     _vp(stream or None)))
+
+    def mult_ext_sum(self, size_ql: int, nterm: int, x0: int, x1: int, x_stride: int, diag: int, diag_stride: int,
+                     present, nsum: int, out0: int, out1: int, batch: int = 1, stream: int = 0) -> None:
+        """out_e[j] = sum_i x_e[i] * diag[j * nterm + i] over Ql|P (EvalMultExt / EvalAddExtInPlace,
+        ckksrns-fhe.cpp:1520-1526); present: nsum * nterm truth values or None."""
+        _check(lib().ofhe_hip_ks_mult_ext_sum(self._h, int(size_ql), int(nterm), _vp(x0 or None), _vp(x1 or None),
+                                              int(x_stride), _vp(diag or None), int(diag_stride),
+                                              self._present(present, int(nsum) * int(nterm)), int(nsum),
+                                              _vp(out0 or None), _vp(out1 or None), int(batch),
+                                              _vp(stream or None)))
+
+    def fast_rotation_ext_sum(self, size_ql: int, digits: int, auto_indices: Sequence[int],
+                              key_b_ptrs: Sequence[int], key_a_ptrs: Sequence[int], addend1: int, nadd: int,
+                              out0: int, out1: int, batch: int = 1, stream: int = 0) -> None:
+        """Sum over the digit sets of EvalFastRotationExt(., k_j, digits_j, false) under key j
+        (ckksrns-fhe.cpp:1544-1545), plus nadd addends on element 1.  digits:
+        [nset][batch][beta][size_ql + size_p][N]; out0, out1: [batch][size_ql + size_p][N]."""
+        n, idx, kb, ka = self._rot_args(auto_indices, key_b_ptrs, key_a_ptrs)
+        _check(lib().ofhe_hip_ks_fast_rotation_ext_sum(self._h, int(size_ql), n, _vp(digits or None), idx, kb, ka,
+                                                       _vp(addend1 or None), int(nadd), _vp(out0 or None),
+                                                       _vp(out1 or None), int(batch), _vp(stream or None)))
+
+    def bsgs_transform(self, size_ql: int, baby_indices: Sequence[int], giant_indices: Sequence[int],
+                       baby_key_b: Sequence[int], baby_key_a: Sequence[int], giant_key_b: Sequence[int],
+                       giant_key_a: Sequence[int], diag: int, diag_stride: int, present, c0: int, c1: int,
+                       out0: int, out1: int, t: int = 0, batch: int = 1, stream: int = 0) -> None:
+        """One BSGS level of FHECKKSRNS::EvalLinearTransform (ckksrns-fhe.cpp:1484-1555): see
+        ofhe_hip_ks_bsgs_transform.  Key pointers of identity steps (index = 1 mod 2N) may be 0."""
+        nb, bi, bkb, bka = self._rot_args(baby_indices, baby_key_b, baby_key_a)
+        ng, gi, gkb, gka = self._rot_args(giant_indices, giant_key_b, giant_key_a)
+        tr = Bsgs(nb, ng, bi, gi, bkb, bka, gkb, gka, _vp(diag or None), int(diag_stride),
+                  self._present(present, nb * ng))
+        _check(lib().ofhe_hip_ks_bsgs_transform(self._h, int(size_ql), ctypes.byref(tr), _vp(c0 or None),
+                                                _vp(c1 or None), _vp(out0 or None), _vp(out1 or None), int(t),
+                                                int(batch), _vp(stream or None)))
 
 
 def comm_unique_id() -> bytes:
