@@ -8,10 +8,9 @@
 //   DCRTPolyImpl::FastBaseConvSK                dcrtpoly-impl.h:2309-2411
 //   LeveledSHEBFVRNS::EvalMult                  bfvrns-leveledshe.cpp:275-297, 326-337, 383-403 (BEHZ)
 #include <algorithm>
-#include <new>
 
 #include "behz_kernels.hpp"
-#include "internal.hpp"
+#include "compose.hpp"
 
 using namespace ofhe;
 
@@ -32,10 +31,9 @@ bool behz_fused_ok(ofhe_behz_t h) { return h->size_b <= BEHZ_FUSED_BMAX; }
 
 int behz_launch(ofhe_behz_t h, int which, const u64* x, u64 in_stride, u64* out, u64 out_stride, u32 batch,
                 hipStream_t s) {
-    const u64 total = (u64)batch << h->log_n;
-    const u64 blocks = (total + 255) / 256;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    const dim3 g((u32)blocks), t(256);
+    dim3 g;
+    RCCHK(coeff_grid((u64)batch << h->log_n, &g));
+    const dim3 t(256);
     const BehzArgs& A = h->args;
     switch (which) {
         case BEHZ_Q_TO_BSK:
@@ -59,23 +57,11 @@ int behz_launch(ofhe_behz_t h, int which, const u64* x, u64 in_stride, u64* out,
     return post_launch();
 }
 
-int behz_live(ofhe_behz_t h) {
-    if (!h || !h->ctx) return fail(OFHE_ERR_STATE, "behz handle is NULL or destroyed");
-    return OFHE_OK;
-}
+int behz_live(ofhe_behz_t h) { return live(h, "behz handle is NULL or destroyed"); }
 
-// the plan transforms exactly `mods` at the handle's N, in the handle's context
-int plan_matches(ofhe_behz_t h, ofhe_plan_t p, const u64* mods, size_t count, const char* what) {
-    if (!p || !p->ctx) return fail(OFHE_ERR_STATE, std::string(what) + " is NULL or destroyed");
-    if (p->ctx != h->ctx) return fail(OFHE_ERR_ARG, std::string(what) + " belongs to another context");
-    if (p->log_n != h->log_n) return fail(OFHE_ERR_ARG, std::string(what) + ": ring dimension differs from the handle's");
-    if (p->towers != count || !std::equal(mods, mods + count, p->q.begin()))
-        return fail(OFHE_ERR_ARG, std::string(what) + ": towers differ from the handle's");
-    return OFHE_OK;
-}
 int plans_match(ofhe_behz_t h, ofhe_plan_t pq, ofhe_plan_t pb) {
-    RCCHK(plan_matches(h, pq, h->q.data(), h->q.size(), "plan_q"));
-    return plan_matches(h, pb, h->bsk.data(), h->bsk.size(), "plan_bsk");
+    RCCHK(plan_is(pq, h->ctx, h->log_n, {&h->q}, "plan_q"));
+    return plan_is(pb, h->ctx, h->log_n, {&h->bsk}, "plan_bsk");
 }
 
 // FastBaseConvqToBskMontgomery with its format handling, result in evaluation
@@ -85,18 +71,12 @@ int plans_match(ofhe_behz_t h, ofhe_plan_t pq, ofhe_plan_t pb) {
 // towers are always transformed (2200-2201).
 int behz_expand_run(ofhe_behz_t h, ofhe_plan_t pq, ofhe_plan_t pb, int eval_form, const u64* x, u64* out, u32 batch,
                     hipStream_t s) {
-    const u64 N = 1ull << h->log_n, Q = h->size_q, K = h->size_b + 1, qk = (Q + K) * N;
-    const u64* src = x;
-    u64 sstride = Q * N;
-    if (eval_form) {
-        RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, x, out, Q * N, qk, batch, s));
-        src = out;
-        sstride = qk;
-    }
-    RCCHK(behz_launch(h, BEHZ_Q_TO_BSK, src, sstride, out + Q * N, qk, batch, s));
-    RCCHK(plan_ntt_range(pb, false, 0, (u32)K, out + Q * N, out + Q * N, qk, qk, batch, s));
-    if (eval_form) return copy_rows(out, qk, x, Q * N, Q * N, batch, s);
-    return plan_ntt_range(pq, false, 0, (u32)Q, x, out, Q * N, qk, batch, s);
+    const u32 K = h->size_b + 1;
+    auto convert = [&](const u64* src, u64 sstride, u64* dst, u64 dstride) {
+        RCCHK(behz_launch(h, BEHZ_Q_TO_BSK, src, sstride, dst, dstride, batch, s));
+        return plan_ntt_range(pb, false, 0, K, dst, dst, dstride, dstride, batch, s);
+    };
+    return expand_skeleton(pq, h->size_q, K, eval_form, x, out, batch, s, convert);
 }
 
 }  // namespace
@@ -114,11 +94,7 @@ int ofhe_hip_behz_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const 
     const u32 K = size_b + 1;
     std::vector<u64> all(q, q + size_q);
     all.insert(all.end(), bsk, bsk + K);
-    for (u64 m : all) {
-        // floor(2^128 / m) is taken as floor((2^128 - 1) / m): equal unless m is a power of two
-        if (!(m & 1) || m < 3) return fail(OFHE_ERR_ARG, "every modulus must be odd");
-        if (m >= (1ull << 60)) return fail(OFHE_ERR_ARG, "every modulus must be below 2^60");
-    }
+    RCCHK(check_moduli(all.data(), all.size()));
     // the centred remainder mod mtilde = 2^16 is lifted as r + b_j - 2^16 (dcrtpoly-impl.h:2172-2174)
     for (u32 j = 0; j < K; j++)
         if (bsk[j] <= (1ull << 16)) return fail(OFHE_ERR_ARG, "every Bsk modulus must exceed 2^16");
@@ -148,9 +124,7 @@ int ofhe_hip_behz_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const 
         const size_t at = put(3 * (size_t)n);
         for (u32 i = 0; i < n; i++) {
             hm[at + i] = m[i];
-            const u128 mu = (~(u128)0) / m[i];
-            hm[at + n + 2 * i] = (u64)mu;
-            hm[at + n + 2 * i + 1] = (u64)(mu >> 64);
+            barrett128(m[i], &hm[at + n + 2 * i]);
         }
         return at;
     };
@@ -191,13 +165,8 @@ int ofhe_hip_behz_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const 
     for (u32 i = 0; i < size_b; i++) hm[o_bhm + i] = tb->BHatModmsk[i] % msk;
     const size_t o_bmq = shoup(tb->BModq, q, size_q);
 
-    ofhe_behz_s* r = new (std::nothrow) ofhe_behz_s();
-    if (!r) return fail(OFHE_ERR_NOMEM, "behz allocation failed");
-    const int rc = alloc_upload(&r->d_mem, hm.data(), hm.size() * sizeof(u64), "behz upload", ctx->device);
-    if (rc != OFHE_OK) {
-        delete r;
-        return rc;
-    }
+    ofhe_behz_s* r = nullptr;
+    RCCHK(create_with_table(&r, &ofhe_behz_s::d_mem, hm, ctx->device, "behz allocation failed", "behz upload"));
     r->ctx = ctx;
     r->log_n = log_n;
     r->size_q = size_q;
@@ -235,11 +204,7 @@ int ofhe_hip_behz_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const 
 }
 
 int ofhe_hip_behz_destroy(ofhe_behz_t h) {
-    if (!h) return fail(OFHE_ERR_ARG, "behz handle is NULL");
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_mem);
-    delete h;
-    return OFHE_OK;
+    return destroy_with_table(h, &ofhe_behz_s::d_mem, "behz handle is NULL");
 }
 
 int ofhe_hip_behz_q_to_bsk(ofhe_behz_t h, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream) {
@@ -255,12 +220,10 @@ int ofhe_hip_behz_expand(ofhe_behz_t h, ofhe_plan_t plan_q, ofhe_plan_t plan_bsk
     RCCHK(behz_live(h));
     RCCHK(plans_match(h, plan_q, plan_bsk));
     if (!x || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
-    {
-        // the INTT of an evaluation-form input goes through out's Q slots and x is read again at the end
-        const u64 N = 1ull << h->log_n, xw = (u64)batch * h->size_q * N,
-                  ow = (u64)batch * (h->size_q + h->size_b + 1) * N;
-        if (x < out + ow && out < x + xw) return fail(OFHE_ERR_ARG, "out overlaps x");
-    }
+    // the INTT of an evaluation-form input goes through out's Q slots and x is read again at the end
+    const u64 bn = (u64)batch << h->log_n;
+    if (words_overlap(x, bn * h->size_q, out, bn * (h->size_q + h->size_b + 1)))
+        return fail(OFHE_ERR_ARG, "out overlaps x");
     HIPCHK(hipSetDevice(h->ctx->device));
     return behz_expand_run(h, plan_q, plan_bsk, eval_form, x, out, batch, pick(stream));
 }
@@ -302,11 +265,7 @@ int ofhe_hip_bfv_eval_mult_behz(ofhe_behz_t h, ofhe_plan_t plan_q, ofhe_plan_t p
                                 uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch, void* stream) {
     RCCHK(behz_live(h));
     RCCHK(plans_match(h, plan_q, plan_bsk));
-    {
-        std::vector<u64> all(h->q);
-        all.insert(all.end(), h->bsk.begin(), h->bsk.end());
-        RCCHK(plan_matches(h, plan_qbsk, all.data(), all.size(), "plan_qbsk"));
-    }
+    RCCHK(plan_is(plan_qbsk, h->ctx, h->log_n, {&h->q, &h->bsk}, "plan_qbsk"));
     if (!c0 || !c1 || !d0 || !d1 || !out0 || !out1 || !out2 || batch == 0)
         return fail(OFHE_ERR_ARG, "bad data argument");
     if ((u64)batch * 4 >= (1ull << 32)) return fail(OFHE_ERR_ARG, "batch too large");
@@ -315,7 +274,7 @@ int ofhe_hip_bfv_eval_mult_behz(ofhe_behz_t h, ofhe_plan_t plan_q, ofhe_plan_t p
     const u64 N = 1ull << h->log_n, Q = h->size_q, K = h->size_b + 1, qk = (Q + K) * N;
     const u64 one = (u64)batch * qk;  // words of one expanded polynomial over the batch
     const bool fused = behz_fused_ok(h);
-    // scratch: the four expanded inputs, the three products, (two launches) their floors
+    // scratch: E | T (compose.hpp), (two launches) the products' floors
     Scratch sc;
     RCCHK(sc.alloc((7 * one + (fused ? 0 : 3 * (u64)batch * K * N)) * sizeof(u64), s, h->ctx));
     u64* E = sc.w();
@@ -324,11 +283,8 @@ int ofhe_hip_bfv_eval_mult_behz(ofhe_behz_t h, ofhe_plan_t plan_q, ofhe_plan_t p
     // FastBaseConvqToBskMontgomery, SetFormat(EVALUATION) of cv1, cv2 (bfvrns-leveledshe.cpp:276-296)
     const u64* in[4] = {c0, c1, d0, d1};
     for (int k = 0; k < 4; k++) RCCHK(behz_expand_run(h, plan_q, plan_bsk, 1, in[k], E + k * one, batch, s));
-    // the tensor product over Q|Bsk (326-337)
-    RCCHK(ofhe_hip_eval_mult_core(plan_qbsk, E, E + one, E + 2 * one, E + 3 * one, T, T + one, T + 2 * one, batch,
-                                  stream));
-    // cvMult[i].SetFormat(COEFFICIENT) (387): the three products as one batch
-    RCCHK(plan_ntt_range(plan_qbsk, true, 0, (u32)(Q + K), T, T, qk, qk, 3 * batch, s));
+    // the tensor product over Q|Bsk (326-337), cvMult[i].SetFormat(COEFFICIENT) (387)
+    RCCHK(tensor_and_intt(plan_qbsk, E, T, one, batch, stream));
     // FastRNSFloorq (390-393), FastBaseConvSK (396-401)
     u64* outs[3] = {out0, out1, out2};
     if (!fused) RCCHK(behz_launch(h, BEHZ_FLOOR, T, qk, F, K * N, 3 * batch, s));

@@ -7,11 +7,10 @@
 //   DCRTPolyImpl::FastExpandCRTBasisPloverQ  dcrtpoly-impl.h:1413-1466
 //   DCRTPolyImpl::ScaleAndRound              dcrtpoly-impl.h:1876-1955
 //   LeveledSHEBFVRNS::EvalMult               bfvrns-leveledshe.cpp:168-408 (HPS, HPSPOVERQ)
-#include <algorithm>
 #include <cstring>
 #include <new>
 
-#include "internal.hpp"
+#include "compose.hpp"
 
 using namespace ofhe;
 
@@ -46,27 +45,20 @@ namespace ofhe {
 // ModSubFast needs the canonical ones.
 int expand_run(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, int eval_form, const u64* x, u64* out, u32 batch,
                hipStream_t s) {
-    const u64 N = 1ull << pq->log_n, Q = pq->towers, P = pp->towers, qp = (Q + P) * N;
-    BconvArgs B = bc->args;
-    B.out_stride = qp;
-    B.in_stride = Q * N;
-    const u64* src = x;
-    if (eval_form) {
-        RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, x, out, Q * N, qp, batch, s));
-        src = out;
-        B.in_stride = qp;
-    }
-    RCCHK(switch_exact_run(bc, B, src, out + Q * N, batch, s));
-    RCCHK(plan_ntt_range(pp, false, 0, (u32)P, out + Q * N, out + Q * N, qp, qp, batch, s));
-    if (eval_form) return copy_rows(out, qp, x, Q * N, Q * N, batch, s);
-    return plan_ntt_range(pq, false, 0, (u32)Q, x, out, Q * N, qp, batch, s);
+    auto convert = [&](const u64* src, u64 sstride, u64* dst, u64 dstride) {
+        BconvArgs B = bc->args;
+        B.in_stride = sstride;
+        B.out_stride = dstride;
+        RCCHK(switch_exact_run(bc, B, src, dst, batch, s));
+        return plan_ntt_range(pp, false, 0, pp->towers, dst, dst, dstride, dstride, batch, s);
+    };
+    return expand_skeleton(pq, pq->towers, pp->towers, eval_form, x, out, batch, s, convert);
 }
 
 int sr_run(ofhe_scale_round_t h, const u64* x, u64* out, u32 batch, hipStream_t s) {
-    const u64 total = (u64)batch << h->args.log_n;
-    const u64 blocks = (total + 255) / 256;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    hipLaunchKernelGGL((k_scale_round<4>), dim3((u32)blocks), dim3(256), 0, s, h->args, x, out, batch);
+    dim3 g;
+    RCCHK(coeff_grid((u64)batch << h->args.log_n, &g));
+    hipLaunchKernelGGL((k_scale_round<4>), g, dim3(256), 0, s, h->args, x, out, batch);
     return post_launch();
 }
 
@@ -77,11 +69,10 @@ int ofhe_hip_expand_crt_basis(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, i
     RCCHK(expand_check(pq, pp, bc));
     if (!x || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
     if (pp->ctx != pq->ctx || bc->ctx != pq->ctx) return fail(OFHE_ERR_ARG, "objects of different contexts");
-    {
-        // the INTT of an evaluation-form input goes through out's Q slots and x is read again at the end
-        const u64 N = 1ull << pq->log_n, xw = (u64)batch * pq->towers * N, ow = (u64)batch * (pq->towers + pp->towers) * N;
-        if (x < out + ow && out < x + xw) return fail(OFHE_ERR_ARG, "out overlaps x");
-    }
+    // the INTT of an evaluation-form input goes through out's Q slots and x is read again at the end
+    const u64 bn = (u64)batch << pq->log_n;
+    if (words_overlap(x, bn * pq->towers, out, bn * (pq->towers + pp->towers)))
+        return fail(OFHE_ERR_ARG, "out overlaps x");
     HIPCHK(hipSetDevice(pq->ctx->device));
     return expand_run(pq, pp, bc, eval_form, x, out, batch, pick(stream));
 }
@@ -103,8 +94,7 @@ int ofhe_hip_scale_round_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
     // size_i + 1 products below 2^120 must fit the 128-bit accumulator (the
     // reference's DoubleNativeInt has the same limit)
     if (si > 255) return fail(OFHE_ERR_ARG, "at most 255 summed towers");
-    // floor(2^128 / o) is taken as floor((2^128 - 1) / o): equal unless o is a power of two
-    for (u32 j = 0; j < so; j++)
+    for (u32 j = 0; j < so; j++)  // barrett128
         if (!(o[j] & 1)) return fail(OFHE_ERR_ARG, "output moduli must be odd");
     // the fractional parts are quotients (X mod s_i) / s_i: in [0, 1), which
     // keeps nu below 2^69 for 256 towers (floor_u128 takes nu < 2^127)
@@ -120,17 +110,11 @@ int ofhe_hip_scale_round_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
     u64* omu = ov + so;
     for (u32 j = 0; j < so; j++) {
         ov[j] = o[j];
-        const u128 mu = (~(u128)0) / o[j];  // floor(2^128 / o): o is odd (checked above)
-        omu[2 * j] = (u64)mu;
-        omu[2 * j + 1] = (u64)(mu >> 64);
+        barrett128(o[j], omu + 2 * j);
     }
-    ofhe_scale_round_s* r = new (std::nothrow) ofhe_scale_round_s();
-    if (!r) return fail(OFHE_ERR_NOMEM, "scale-and-round allocation failed");
-    const int rc = alloc_upload(&r->d_mem, h.data(), h.size() * sizeof(u64), "scale-and-round upload", ctx->device);
-    if (rc != OFHE_OK) {
-        delete r;
-        return rc;
-    }
+    ofhe_scale_round_s* r = nullptr;
+    RCCHK(create_with_table(&r, &ofhe_scale_round_s::d_mem, h, ctx->device, "scale-and-round allocation failed",
+                            "scale-and-round upload"));
     r->ctx = ctx;
     r->size_q = size_q;
     r->size_p = size_p;
@@ -152,15 +136,11 @@ int ofhe_hip_scale_round_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
 }
 
 int ofhe_hip_scale_round_destroy(ofhe_scale_round_t h) {
-    if (!h) return fail(OFHE_ERR_ARG, "scale-and-round handle is NULL");
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_mem);
-    delete h;
-    return OFHE_OK;
+    return destroy_with_table(h, &ofhe_scale_round_s::d_mem, "scale-and-round handle is NULL");
 }
 
 int ofhe_hip_scale_and_round(ofhe_scale_round_t h, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream) {
-    if (!h || !h->ctx) return fail(OFHE_ERR_STATE, "scale-and-round handle is NULL or destroyed");
+    RCCHK(live(h, "scale-and-round handle is NULL or destroyed"));
     if (!x || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
     HIPCHK(hipSetDevice(h->ctx->device));
     return sr_run(h, x, out, batch, pick(stream));
@@ -180,9 +160,7 @@ int ofhe_hip_bfv_mult_create(ofhe_ctx_t ctx, int technique, ofhe_plan_t plan_q, 
                          q_to_r_neg ? q_to_r_neg->ctx : ctx})
         if (c != ctx) return fail(OFHE_ERR_ARG, "every composed handle must belong to ctx");
     const u32 Q = plan_q->towers, R = plan_r->towers;
-    if (plan_qr->log_n != plan_q->log_n || plan_qr->towers != Q + R ||
-        !std::equal(plan_q->q.begin(), plan_q->q.end(), plan_qr->q.begin()) ||
-        !std::equal(plan_r->q.begin(), plan_r->q.end(), plan_qr->q.begin() + Q))
+    if (plan_qr->log_n != plan_q->log_n || !plan_towers_are(plan_qr, {&plan_q->q, &plan_r->q}))
         return fail(OFHE_ERR_ARG, "plan_qr is not plan_q's towers followed by plan_r's");
     if (scale_round->args.log_n != plan_q->log_n || scale_round->size_q != Q || scale_round->size_p != R)
         return fail(OFHE_ERR_ARG, "scale-and-round handle does not match the bases");
@@ -218,7 +196,7 @@ int ofhe_hip_bfv_mult_destroy(ofhe_bfv_mult_t h) {
 int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t h, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
                            const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
                            void* stream) {
-    if (!h || !h->ctx) return fail(OFHE_ERR_STATE, "bfv mult handle is NULL or destroyed");
+    RCCHK(live(h, "bfv mult handle is NULL or destroyed"));
     if (!c0 || !c1 || !d0 || !d1 || !out0 || !out1 || !out2 || batch == 0)
         return fail(OFHE_ERR_ARG, "bad data argument");
     if ((u64)batch * 4 >= (1ull << 32)) return fail(OFHE_ERR_ARG, "batch too large");
@@ -227,7 +205,7 @@ int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t h, const uint64_t* c0, const uint64_t
     ofhe_plan_t pq = h->plan_q, pr = h->plan_r, pqr = h->plan_qr;
     const u64 N = 1ull << pq->log_n, Q = pq->towers, R = pr->towers, qr = (Q + R) * N;
     const u64 one = (u64)batch * qr;  // words of one expanded polynomial over the batch
-    // scratch: the four expanded inputs, the three products, (HPS) their R parts
+    // scratch: E | T (compose.hpp: the four expanded inputs, the three products), (HPS) the products' R parts
     const bool hps = h->technique == OFHE_BFV_HPS;
     Scratch sc;
     RCCHK(sc.alloc((7 * one + (hps ? 3 * (u64)batch * R * N : 0)) * sizeof(u64), s, h->ctx));
@@ -245,23 +223,12 @@ int ofhe_hip_bfv_eval_mult(ofhe_bfv_mult_t h, const uint64_t* c0, const uint64_t
             continue;
         }
         // SetFormat(COEFFICIENT), FastExpandCRTBasisPloverQ, SetFormat(EVALUATION) (228-232):
-        // the coefficient form goes to the Q slots, the approximate switch with
-        // mNegRlQHatInvModq / qInvModr fills the R slots (dcrtpoly-impl.h:1419-1441),
-        // the exact switch R -> Q replaces the Q slots (1445-1460)
+        // the coefficient form goes to the Q slots, which the exact switch R -> Q then replaces
         RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, dd[k], Ek, Q * N, qr, batch, s));
-        BconvArgs B = h->q_to_r_neg->args;
-        B.in_stride = B.out_stride = qr;
-        B.lazy_out = 0;
-        RCCHK(bconv_run(B, Ek, Ek + Q * N, batch, s));
-        BconvArgs X = h->r_to_q->args;
-        X.in_stride = X.out_stride = qr;
-        RCCHK(switch_exact_run(h->r_to_q, X, Ek + Q * N, Ek, batch, s));
-        RCCHK(plan_ntt_range(pqr, false, 0, (u32)(Q + R), Ek, Ek, qr, qr, batch, s));
+        RCCHK(fast_expand_p_over_q(h->q_to_r_neg, h->r_to_q, pqr, Ek, qr, Ek, batch, s));
     }
-    // the tensor product over Q|R (316-330; EvalMultCore's three outputs)
-    RCCHK(ofhe_hip_eval_mult_core(pqr, E, E + one, E + 2 * one, E + 3 * one, T, T + one, T + 2 * one, batch, stream));
-    // cvMult[i].SetFormat(COEFFICIENT) (342, 356): the three products as one batch
-    RCCHK(plan_ntt_range(pqr, true, 0, (u32)(Q + R), T, T, qr, qr, 3 * batch, s));
+    // the tensor product over Q|R (316-330; EvalMultCore's three outputs), cvMult[i].SetFormat(COEFFICIENT) (342, 356)
+    RCCHK(tensor_and_intt(pqr, E, T, one, batch, stream));
     u64* outs[3] = {out0, out1, out2};
     if (hps) {
         // ScaleAndRound to R (343-345), SwitchCRTBasis R -> Q (347-350)

@@ -7,12 +7,10 @@
 //   DCRTPolyImpl::ScaleAndRound -> NativePoly   dcrtpoly-impl.h:1537-1814 (HPS family), 2005-2049 (BEHZ)
 //   NativeVectorT::MultiplyAndRound             mubintvecnat.cpp:420-435 (one tower)
 //   DCRTPolyImpl::TimesQovert                   dcrtpoly-impl.h:1015-1031
-#include <algorithm>
 #include <cstring>
-#include <new>
 
 #include "bfv_decrypt_kernels.hpp"
-#include "internal.hpp"
+#include "compose.hpp"
 
 using namespace ofhe;
 
@@ -37,10 +35,7 @@ int dec_branch(u32 size_q, u64 q0, u64 t) {
     return (pow2 ? 0 : 4) + (split ? 2 : 0) + (reduced ? 1 : 0);
 }
 
-int dec_live(ofhe_bfv_decrypt_t h) {
-    if (!h || !h->ctx) return fail(OFHE_ERR_STATE, "decrypt handle is NULL or destroyed");
-    return OFHE_OK;
-}
+int dec_live(ofhe_bfv_decrypt_t h) { return live(h, "decrypt handle is NULL or destroyed"); }
 
 int dec_scale_round_run(ofhe_bfv_decrypt_t h, const u64* x, u64* out, u32 batch, hipStream_t s) {
     const dim3 g(grid_for((u64)batch << h->args.log_n)), t(256);
@@ -70,11 +65,7 @@ int ofhe_hip_bfv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
     if ((u128)2 * size_q * t >= ((u128)1 << 64)) return fail(OFHE_ERR_ARG, "2 size_q t must be below 2^64");
     if (technique != OFHE_BFV_HPS && technique != OFHE_BFV_HPSPOVERQ && technique != OFHE_BFV_BEHZ)
         return fail(OFHE_ERR_ARG, "technique must be HPS, HPSPOVERQ or BEHZ");
-    for (u32 i = 0; i < size_q; i++) {
-        // floor(2^128 / m) is taken as floor((2^128 - 1) / m): equal unless m is a power of two
-        if (!(q[i] & 1) || q[i] < 3) return fail(OFHE_ERR_ARG, "every modulus must be odd");
-        if (q[i] >= (1ull << 60)) return fail(OFHE_ERR_ARG, "every modulus must be below 2^60");
-    }
+    RCCHK(check_moduli(q, size_q));
     const bool behz = technique == OFHE_BFV_BEHZ;
     int branch = OFHE_BFV_DECRYPT_ONE_TOWER;
     if (size_q > 1) {
@@ -106,9 +97,7 @@ int ofhe_hip_bfv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
     };
     for (u32 i = 0; i < size_q; i++) {
         hq[i] = q[i];
-        const u128 mu = (~(u128)0) / q[i];
-        hmu[2 * i] = (u64)mu;
-        hmu[2 * i + 1] = (u64)(mu >> 64);
+        barrett128(q[i], hmu + 2 * i);
         if (branch == OFHE_BFV_DECRYPT_BEHZ) {
             pair(hw + 2 * i, tb->tgammaQHatInvModq[i], q[i]);
             pair(hwb + 2 * i, tb->negInvqModtgamma[i], tgamma);
@@ -123,13 +112,9 @@ int ofhe_hip_bfv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
         if (tb->tInvModq) pair(hti + 2 * i, tb->tInvModq[i], q[i]);
     }
 
-    ofhe_bfv_decrypt_s* r = new (std::nothrow) ofhe_bfv_decrypt_s();
-    if (!r) return fail(OFHE_ERR_NOMEM, "decrypt allocation failed");
-    const int rc = alloc_upload(&r->d_mem, hm.data(), hm.size() * sizeof(u64), "decrypt upload", ctx->device);
-    if (rc != OFHE_OK) {
-        delete r;
-        return rc;
-    }
+    ofhe_bfv_decrypt_s* r = nullptr;
+    RCCHK(create_with_table(&r, &ofhe_bfv_decrypt_s::d_mem, hm, ctx->device, "decrypt allocation failed",
+                            "decrypt upload"));
     r->ctx = ctx;
     r->branch = branch;
     r->has_tqt = tb->tInvModq != nullptr;
@@ -165,11 +150,7 @@ int ofhe_hip_bfv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q,
 }
 
 int ofhe_hip_bfv_decrypt_destroy(ofhe_bfv_decrypt_t h) {
-    if (!h) return fail(OFHE_ERR_ARG, "decrypt handle is NULL");
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_mem);
-    delete h;
-    return OFHE_OK;
+    return destroy_with_table(h, &ofhe_bfv_decrypt_s::d_mem, "decrypt handle is NULL");
 }
 
 int ofhe_hip_bfv_decrypt_branch(ofhe_bfv_decrypt_t h, int* branch) {
@@ -191,11 +172,7 @@ int ofhe_hip_bfv_decrypt(ofhe_bfv_decrypt_t h, ofhe_plan_t plan_q, uint32_t elem
                          const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* s, uint64_t* out,
                          uint32_t batch, void* stream) {
     RCCHK(dec_live(h));
-    if (!plan_q || !plan_q->ctx) return fail(OFHE_ERR_STATE, "plan_q is NULL or destroyed");
-    if (plan_q->ctx != h->ctx) return fail(OFHE_ERR_ARG, "plan_q belongs to another context");
-    if (plan_q->log_n != h->args.log_n) return fail(OFHE_ERR_ARG, "plan_q: ring dimension differs from the handle's");
-    if (plan_q->towers != h->q.size() || !std::equal(h->q.begin(), h->q.end(), plan_q->q.begin()))
-        return fail(OFHE_ERR_ARG, "plan_q: towers differ from the handle's");
+    RCCHK(plan_is(plan_q, h->ctx, h->args.log_n, {&h->q}, "plan_q"));
     if (elements != 2 && elements != 3) return fail(OFHE_ERR_ARG, "2 or 3 ciphertext elements");
     if (!c0 || !c1 || (elements == 3 && !c2) || !s || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
     HIPCHK(hipSetDevice(h->ctx->device));

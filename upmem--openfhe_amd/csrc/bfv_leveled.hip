@@ -11,9 +11,8 @@
 //   DCRTPolyImpl::ExpandCRTBasisQlHat             dcrtpoly-impl.h:1514-1534
 //   DCRTPolyImpl::ScaleAndRound                   dcrtpoly-impl.h:1876-1955
 #include <algorithm>
-#include <new>
 
-#include "internal.hpp"
+#include "compose.hpp"
 #include "bfv_leveled_kernels.hpp"
 
 using namespace ofhe;
@@ -37,10 +36,8 @@ struct ofhe_bfv_level_s {
 
 namespace {
 
-bool overlaps(const u64* a, u64 aw, const u64* b, u64 bw) { return a < b + bw && b < a + aw; }
-
 int level_ok(ofhe_bfv_level_t h, u32 batch) {
-    if (!h || !h->ctx) return fail(OFHE_ERR_STATE, "bfv level handle is NULL or destroyed");
+    RCCHK(live(h, "bfv level handle is NULL or destroyed"));
     if (batch == 0 || (u64)batch * 4 >= (1ull << 32)) return fail(OFHE_ERR_ARG, "batch must be in [1, 2^30)");
     return OFHE_OK;
 }
@@ -50,17 +47,16 @@ int ql_hat_run(ofhe_bfv_level_t h, const u64* x, const u64* addend, u64* out, u3
     const u32 bpr = (u32)((half + 255) / 256);
     // out == addend: the towers past l are in place already
     const u32 rt = addend == out ? h->l + 1 : h->size_q;
-    const u64 blocks = (u64)batch * rt * bpr;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    hipLaunchKernelGGL(k_expand_ql_hat, dim3((u32)blocks), dim3(256), 0, s, h->args, x, addend, out, bpr, rt);
+    dim3 g;
+    RCCHK(coeff_grid((u64)batch * rt * bpr * 256, &g));
+    hipLaunchKernelGGL(k_expand_ql_hat, g, dim3(256), 0, s, h->args, x, addend, out, bpr, rt);
     return post_launch();
 }
 
 int sr_lift_run(ofhe_bfv_level_t h, const u64* x, u64* out, u32 batch, hipStream_t s) {
-    const u64 total = (u64)batch << h->log_n;
-    const u64 blocks = (total + 255) / 256;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large");
-    hipLaunchKernelGGL((k_scale_round_lift<4>), dim3((u32)blocks), dim3(256), 0, s, h->sr->args, h->args, x, out, batch);
+    dim3 g;
+    RCCHK(coeff_grid((u64)batch << h->log_n, &g));
+    hipLaunchKernelGGL((k_scale_round_lift<4>), g, dim3(256), 0, s, h->sr->args, h->args, x, out, batch);
     return post_launch();
 }
 
@@ -88,8 +84,7 @@ int ofhe_hip_bfv_level_create(ofhe_ctx_t ctx, uint32_t l, ofhe_plan_t plan_q, of
     if (plan_ql->towers != L || plan_rl->towers != L) return fail(OFHE_ERR_ARG, "plan_ql and plan_rl must have l + 1 towers");
     if (!std::equal(plan_ql->q.begin(), plan_ql->q.end(), plan_q->q.begin()))
         return fail(OFHE_ERR_ARG, "plan_ql is not a prefix of plan_q");
-    if (plan_qlrl->towers != 2 * L || !std::equal(plan_ql->q.begin(), plan_ql->q.end(), plan_qlrl->q.begin()) ||
-        !std::equal(plan_rl->q.begin(), plan_rl->q.end(), plan_qlrl->q.begin() + L))
+    if (!plan_towers_are(plan_qlrl, {&plan_ql->q, &plan_rl->q}))
         return fail(OFHE_ERR_ARG, "plan_qlrl is not plan_ql's towers followed by plan_rl's");
     if (ql_to_rl->hq != plan_ql->q || ql_to_rl->hp != plan_rl->q)
         return fail(OFHE_ERR_ARG, "ql_to_rl does not map plan_ql's towers to plan_rl's");
@@ -114,13 +109,9 @@ int ofhe_hip_bfv_level_create(ofhe_ctx_t ctx, uint32_t l, ofhe_plan_t plan_q, of
         tab[3 * i + 1] = ql_hat_modq[i];
         tab[3 * i + 2] = shoup_pre(ql_hat_modq[i], q);
     }
-    ofhe_bfv_level_s* h = new (std::nothrow) ofhe_bfv_level_s();
-    if (!h) return fail(OFHE_ERR_NOMEM, "bfv level allocation failed");
-    const int rc = alloc_upload(&h->d_tab, tab.data(), tab.size() * sizeof(u64), "bfv level upload", ctx->device);
-    if (rc != OFHE_OK) {
-        delete h;
-        return rc;
-    }
+    ofhe_bfv_level_s* h = nullptr;
+    RCCHK(create_with_table(&h, &ofhe_bfv_level_s::d_tab, tab, ctx->device, "bfv level allocation failed",
+                            "bfv level upload"));
     h->ctx = ctx;
     h->l = l;
     h->size_q = Q;
@@ -140,11 +131,7 @@ int ofhe_hip_bfv_level_create(ofhe_ctx_t ctx, uint32_t l, ofhe_plan_t plan_q, of
 }
 
 int ofhe_hip_bfv_level_destroy(ofhe_bfv_level_t h) {
-    if (!h) return fail(OFHE_ERR_ARG, "bfv level handle is NULL");
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_tab);
-    delete h;
-    return OFHE_OK;
+    return destroy_with_table(h, &ofhe_bfv_level_s::d_tab, "bfv level handle is NULL");
 }
 
 int ofhe_hip_expand_ql_hat(ofhe_bfv_level_t h, const uint64_t* x, const uint64_t* addend, uint64_t* out, uint32_t batch,
@@ -152,9 +139,9 @@ int ofhe_hip_expand_ql_hat(ofhe_bfv_level_t h, const uint64_t* x, const uint64_t
     RCCHK(level_ok(h, batch));
     if (!x || !out) return fail(OFHE_ERR_ARG, "bad data argument");
     const u64 N = 1ull << h->log_n;
-    if (overlaps(x, (u64)batch * (h->l + 1) * N, out, (u64)batch * h->size_q * N))
+    if (words_overlap(x, (u64)batch * (h->l + 1) * N, out, (u64)batch * h->size_q * N))
         return fail(OFHE_ERR_ARG, "out overlaps x");
-    if (addend && addend != out && overlaps(addend, (u64)batch * h->size_q * N, out, (u64)batch * h->size_q * N))
+    if (addend && addend != out && words_overlap(addend, (u64)batch * h->size_q * N, out, (u64)batch * h->size_q * N))
         return fail(OFHE_ERR_ARG, "out overlaps addend without being addend");
     HIPCHK(hipSetDevice(h->ctx->device));
     return ql_hat_run(h, x, addend, out, batch, pick(stream));
@@ -165,7 +152,7 @@ int ofhe_hip_scale_round_expand_ql_hat(ofhe_bfv_level_t h, const uint64_t* x, ui
     RCCHK(level_ok(h, batch));
     if (!x || !out) return fail(OFHE_ERR_ARG, "bad data argument");
     const u64 N = 1ull << h->log_n;
-    if (overlaps(x, (u64)batch * 2 * (h->l + 1) * N, out, (u64)batch * h->size_q * N))
+    if (words_overlap(x, (u64)batch * 2 * (h->l + 1) * N, out, (u64)batch * h->size_q * N))
         return fail(OFHE_ERR_ARG, "out overlaps x");
     HIPCHK(hipSetDevice(h->ctx->device));
     return sr_lift_run(h, x, out, batch, pick(stream));
@@ -183,9 +170,8 @@ int ofhe_hip_bfv_eval_mult_leveled(ofhe_bfv_level_t h, const uint64_t* c0, const
     const bool dropped = L < Q;
     const u64 one = (u64)batch * qr;   // words of one expanded polynomial over the batch
     const u64 full = (u64)batch * Q * N;  // ... of one polynomial over Q
-    // scratch: the four expanded inputs, the three products, the coefficient
-    // forms of d0, d1 over Q, and below the full level those of c0, c1 and
-    // their images over Q_l
+    // scratch: E | T (compose.hpp), the coefficient forms of d0, d1 over Q, and
+    // below the full level those of c0, c1 and their images over Q_l
     Scratch sc;
     RCCHK(sc.alloc((7 * one + 2 * full + (dropped ? 2 * full + 2 * (u64)batch * L * N : 0)) * sizeof(u64), s, h->ctx));
     u64* E = sc.w();
@@ -206,27 +192,13 @@ int ofhe_hip_bfv_eval_mult_leveled(ofhe_bfv_level_t h, const uint64_t* c0, const
         RCCHK(expand_run(pql, prl, h->ql_to_rl, 0, Cl, E, 2 * batch, s));
     }
     // cv2[i]: SetFormat(COEFFICIENT), FastExpandCRTBasisPloverQ, SetFormat(EVALUATION) (268-273).
-    // The approximate switch with mNegRlQHatInvModq(l) / qInvModr reads all size_q towers and
-    // fills the R_l slots (dcrtpoly-impl.h:1419-1441); the exact switch R_l -> Q_l fills the
-    // Q_l slots (1445-1460).  Both elements as one batch after the transforms.
+    // The approximate switch reads all size_q towers (mNegRlQHatInvModq(l)); both elements as one
+    // batch after the transforms.
     RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, d0, D, Q * N, Q * N, batch, s));
     RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, d1, D + full, Q * N, Q * N, batch, s));
-    {
-        u64* E2 = E + 2 * one;
-        BconvArgs B = h->q_to_rl_neg->args;
-        B.in_stride = Q * N;
-        B.out_stride = qr;
-        B.lazy_out = 0;
-        RCCHK(bconv_run(B, D, E2 + L * N, 2 * batch, s));
-        BconvArgs X = h->rl_to_ql->args;
-        X.in_stride = X.out_stride = qr;
-        RCCHK(switch_exact_run(h->rl_to_ql, X, E2 + L * N, E2, 2 * batch, s));
-        RCCHK(plan_ntt_range(pqr, false, 0, (u32)(2 * L), E2, E2, qr, qr, 2 * batch, s));
-    }
-    // the tensor product over Q_l R_l (316-330)
-    RCCHK(ofhe_hip_eval_mult_core(pqr, E, E + one, E + 2 * one, E + 3 * one, T, T + one, T + 2 * one, batch, stream));
-    // cvMult[i].SetFormat(COEFFICIENT) (369): the three products as one batch
-    RCCHK(plan_ntt_range(pqr, true, 0, (u32)(2 * L), T, T, qr, qr, 3 * batch, s));
+    RCCHK(fast_expand_p_over_q(h->q_to_rl_neg, h->rl_to_ql, pqr, D, Q * N, E + 2 * one, 2 * batch, s));
+    // the tensor product over Q_l R_l (316-330), cvMult[i].SetFormat(COEFFICIENT) (369)
+    RCCHK(tensor_and_intt(pqr, E, T, one, batch, stream));
     u64* outs[3] = {out0, out1, out2};
     for (int k = 0; k < 3; k++) {
         // ScaleAndRound to Q_l (372-374), ExpandCRTBasisQlHat below the full level (376-380)
@@ -254,10 +226,10 @@ int ofhe_hip_bfv_relinearize_leveled(ofhe_bfv_level_t h, ofhe_ks_t ks, uint32_t 
     if ((elements == 3) != (c2 != nullptr)) return fail(OFHE_ERR_ARG, "c2 must be given exactly when elements is 3");
     const u64 N = 1ull << h->log_n, Q = h->size_q, L = h->l + 1;
     const u64 full = (u64)batch * Q * N, low = (u64)batch * L * N;
-    if (overlaps(out0, full, out1, full)) return fail(OFHE_ERR_ARG, "out0 overlaps out1");
+    if (words_overlap(out0, full, out1, full)) return fail(OFHE_ERR_ARG, "out0 overlaps out1");
     for (const u64* in : {c0, c1, c2})
         for (const u64* o : {(const u64*)out0, (const u64*)out1})
-            if (in && overlaps(in, full, o, full)) return fail(OFHE_ERR_ARG, "an output overlaps an input");
+            if (in && words_overlap(in, full, o, full)) return fail(OFHE_ERR_ARG, "an output overlaps an input");
     {
         // the engine must reach level l + 1 (its own check of size_ql)
         u32 beta = 0;

@@ -1,10 +1,13 @@
 // internal.hpp -- definitions shared by the translation units of the backend
-// (ofhe_hip.hip: context, plans, NTT, element-wise ops, base conversion;
-// keyswitch.hip: ApproxModUp / ApproxModDown / hybrid key switching, rescaling;
-// bfv.hip: BFV multiplication (HPS family), ScaleAndRound; bfv_leveled.hip:
-// HPSPOVERQLEVELED with dropped levels; behz.hip: BFV
-// multiplication (BEHZ); bfv_decrypt.hip: BFV decryption, TimesQovert; comm.hip:
-// multi-device collectives).
+// (ofhe_hip.hip: context, plans, NTT, element-wise ops, tensor product, base
+// conversion (approximate and exact); keyswitch.hip: ApproxModUp /
+// ApproxModDown, hybrid key switching, hoisted rotations, the BSGS linear
+// transform, rescaling, BV key switching; bfv.hip: ExpandCRTBasis,
+// ScaleAndRound, BFV multiplication (HPS, HPSPOVERQ); bfv_leveled.hip:
+// HPSPOVERQLEVELED multiplication and relinearisation with dropped levels;
+// behz.hip: BFV multiplication (BEHZ); bfv_decrypt.hip: BFV decryption,
+// TimesQovert; comm.hip: multi-device collectives).  compose.hpp, on top of
+// this header, holds the host code those files share when they compose kernels.
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

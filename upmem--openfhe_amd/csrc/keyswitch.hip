@@ -16,7 +16,7 @@
 #include <map>
 #include <new>
 
-#include "internal.hpp"
+#include "compose.hpp"
 #include "ks_kernels.hpp"
 #include "lt_kernels.hpp"
 
@@ -162,31 +162,24 @@ int ofhe_hip_approx_mod_up(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, int 
         return fail(OFHE_ERR_ARG, "base converter does not map plan_q's towers to plan_p's");
     HIPCHK(hipSetDevice(pq->ctx->device));
     hipStream_t s = pick(stream);
-    const u64 N = 1ull << pq->log_n, Q = pq->towers, P = pp->towers, qp = (Q + P) * N;
-    BconvArgs B = bc->args;
-    B.out_stride = qp;
-    B.lazy_out = 1;  // the P towers go through a forward NTT below
-    const u64* src = x;
-    B.in_stride = Q * N;
-    if (eval_form) {
-        // coefficient copy of x (SetFormat(COEFFICIENT), 1097-1100) into the Q slots
-        RCCHK(plan_ntt_range(pq, true, 0, (u32)Q, x, out, Q * N, qp, batch, s));
-        src = out;
-        B.in_stride = qp;
-    }
-    if (bc->bcols && bconv_cols_ok(pp, B)) {
-        // the conversion writes the P towers' column-pass output (k_bconv_cols),
-        // the block pass finishes their forward transform (1112-1116)
-        RCCHK(bconv_cols_run(pp, 0, B, src, out + Q * N, batch, s));
-        RCCHK(plan_ntt_fwd_block(pp, 0, (u32)P, out + Q * N, qp, batch, s));
-    } else {
-        RCCHK(bconv_run(B, src, out + Q * N, batch, s));
-        // P towers to evaluation form (1112-1116)
-        RCCHK(plan_ntt_range(pp, false, 0, (u32)P, out + Q * N, out + Q * N, qp, qp, batch, s));
-    }
-    // Q towers: the stored evaluation input, or its NTT (1119-1127)
-    if (eval_form) return copy_rows(out, qp, x, Q * N, Q * N, batch, s);
-    return plan_ntt_range(pq, false, 0, (u32)Q, x, out, Q * N, qp, batch, s);
+    const u32 P = pp->towers;
+    auto convert = [&](const u64* src, u64 sstride, u64* dst, u64 dstride) {
+        BconvArgs B = bc->args;
+        B.in_stride = sstride;
+        B.out_stride = dstride;
+        B.lazy_out = 1;  // the P towers go through a forward NTT below
+        if (bc->bcols && bconv_cols_ok(pp, B)) {
+            // the conversion writes the P towers' column-pass output (k_bconv_cols),
+            // the block pass finishes their forward transform (1112-1116)
+            RCCHK(bconv_cols_run(pp, 0, B, src, dst, batch, s));
+            return plan_ntt_fwd_block(pp, 0, P, dst, dstride, batch, s);
+        }
+        RCCHK(bconv_run(B, src, dst, batch, s));
+        return plan_ntt_range(pp, false, 0, P, dst, dst, dstride, dstride, batch, s);  // (1112-1116)
+    };
+    // the coefficient copy of an evaluation-form x (SetFormat(COEFFICIENT), 1097-1100) goes into the Q
+    // slots; the Q towers are the stored evaluation input, or its NTT (1119-1127)
+    return expand_skeleton(pq, pq->towers, P, eval_form, x, out, batch, s, convert);
 }
 
 int ofhe_hip_approx_mod_down(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, const uint64_t* p_inv_modq,
@@ -395,10 +388,10 @@ static int level_get(ofhe_ks_t k, u32 size_ql, KsLevel** out) {
         for (u32 i = 0; i < l + P; i++) {
             const bool isq = i < l;
             const u64 m = isq ? k->q[i] : k->p[i - l];
-            const u128 mu = (~(u128)0) / m;
-            u64 lr[3];
+            u64 mu[2], lr[3];
+            barrett128(m, mu);
             limb_red_consts(m, lr);
-            tow[i] = KsTower{m, (u64)mu, (u64)(mu >> 64), (isq ? i : k->size_q + i - l) * N, lr[0], lr[1], lr[2]};
+            tow[i] = KsTower{m, mu[0], mu[1], (isq ? i : k->size_q + i - l) * N, lr[0], lr[1], lr[2]};
         }
         std::vector<TowerScalar> pinv(l), pmodq(l);
         for (u32 i = 0; i < l; i++) {
@@ -757,12 +750,6 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
 // BSGS linear transform (FHECKKSRNS::EvalLinearTransform, ckksrns-fhe.cpp:1484-1555;
 // the loops of EvalCoeffsToSlots / EvalSlotsToCoeffs, 1636-1698): lt_kernels.hpp
 // ---------------------------------------------------------------------------
-// [a, a + an) and [b, b + bn) (words) overlap
-static bool words_overlap(const u64* a, u64 an, const u64* b, u64 bn) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + 8 * bn && b0 < a0 + 8 * an;
-}
-
 static int ks_ext_impl(ofhe_ks_t k, KsLevel* L, const u64* c, u64* out, u32 batch, hipStream_t s) {
     const u32 towers = L->size_ql + k->size_p;
     const u64 nthreads = (u64)batch * towers << k->log_n;
@@ -1095,10 +1082,8 @@ static int rescale_check(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, const 
     // word at the same address from the same thread.  With a packed output
     // (out_stride = (towers-1)N < x_stride) entry b's output would overwrite
     // towers of entry b-1's input that other workgroups still read.
-    const u64 x_end = (u64)(uintptr_t)x + 8 * ((u64)(batch - 1) * xs + (u64)towers * N);
-    const u64 o_end = (u64)(uintptr_t)out + 8 * ((u64)(batch - 1) * os + (u64)(towers - 1) * N);
-    const bool overlap = (u64)(uintptr_t)x < o_end && (u64)(uintptr_t)out < x_end;
-    if (overlap && !((const u64*)x == out && xs == os))
+    const u64 xw = (u64)(batch - 1) * xs + (u64)towers * N, ow = (u64)(batch - 1) * os + (u64)(towers - 1) * N;
+    if (words_overlap(x, xw, out, ow) && !(x == out && xs == os))
         return fail(OFHE_ERR_ARG, "out overlaps x: in place needs out == x and out_stride == x_stride");
     return OFHE_OK;
 }
@@ -1123,8 +1108,8 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
     A.log_n = log_n;
     A.towers = L;
     const u32 bpr = (u32)((N / 2 + 255) / 256);  // two coefficients per thread
-    const u64 blocks = (u64)bpr * batch * L;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large for one launch");
+    dim3 g;
+    RCCHK(coeff_grid((u64)bpr * batch * L * 256, &g, "batch too large for one launch"));
     if (!eval) {
         A.last = x + (u64)L * N;
         A.lstride = xs;
@@ -1133,7 +1118,7 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
         A.y = out;
         A.ystride = os;
         with_int<SW_AXPY, SW_XPYA>(mode, [&](auto m) {
-            hipLaunchKernelGGL(k_switch_scale<decltype(m)::value>, dim3((u32)blocks), dim3(256), 0, s, A, bpr);
+            hipLaunchKernelGGL(k_switch_scale<decltype(m)::value>, g, dim3(256), 0, s, A, bpr);
         });
         RCCHK(post_launch());
         // DropLastElementAndScale switches the coefficient-form towers to
@@ -1156,7 +1141,7 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
     A.lstride = N;
     A.y = sy.w();
     A.ystride = ys;
-    hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, dim3((u32)blocks), dim3(256), 0, s, A, bpr);
+    hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, g, dim3(256), 0, s, A, bpr);
     RCCHK(post_launch());
     if (log_n >= 12) return plan_ntt_fwd_sub(p, 0, L, sy.w(), ys, x, xs, out, os, dsc, batch, s);
     RCCHK(plan_ntt_range(p, false, 0, L, sy.w(), sy.w(), ys, ys, batch, s));
@@ -1235,7 +1220,8 @@ int ofhe_hip_bv_precompute(ofhe_plan_t p, uint32_t towers, const uint64_t* c, ui
     const u64 dstride = (u64)T * TN;  // words per batch entry of digits
     const bool fused = log_n > 12 && p->split != SPLIT_T9 && OFHE_RESCALE_FUSE;
     const u32 bpr = (u32)((N / 2 + 255) / 256);
-    if ((u64)bpr * batch * T >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large for one launch");
+    dim3 g;
+    RCCHK(coeff_grid((u64)bpr * batch * T * 256, &g, "batch too large for one launch"));
     for (u32 i = 0; i < T; i++) {
         u64* di = digits + (u64)i * TN;
         if (fused) {
@@ -1253,7 +1239,7 @@ int ofhe_hip_bv_precompute(ofhe_plan_t p, uint32_t towers, const uint64_t* c, ui
         A.pre = 1;
         A.log_n = log_n;
         A.towers = T;
-        hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, dim3(bpr * batch * T), dim3(256), 0, s, A, bpr);
+        hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, g, dim3(256), 0, s, A, bpr);
         RCCHK(post_launch());
         RCCHK(plan_ntt_range(p, false, 0, T, di, di, dstride, dstride, batch, s));
     }
@@ -1271,16 +1257,16 @@ int ofhe_hip_bv_core(ofhe_plan_t p, uint32_t towers, const uint64_t* digits, con
     HIPCHK(hipSetDevice(p->ctx->device));
     std::vector<u64> mu(3 * (size_t)towers);
     for (u32 t = 0; t < towers; t++) {
-        const u128 m = ~(u128)0 / p->q[t];  // floor((2^128 - 1) / q) = floor(2^128 / q) for q not a power of two
-        mu[3 * t] = p->q[t], mu[3 * t + 1] = (u64)m, mu[3 * t + 2] = (u64)(m >> 64);
+        mu[3 * t] = p->q[t];
+        barrett128(p->q[t], &mu[3 * t + 1]);
     }
     const u64* dmu = nullptr;
     RCCHK(plan_table(p, mu, &dmu));
     BvArgs A{digits, key_b, key_a, out0, out1, dmu, towers, towers, key_towers, p->log_n};
     const u64 N = 1ull << p->log_n;
     const u32 bpr = (u32)((N + 255) / 256);
-    const u64 blocks = (u64)bpr * batch * towers;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large for one launch");
-    hipLaunchKernelGGL(k_bv_inner, dim3((u32)blocks), dim3(256), 0, pick(stream), A, bpr);
+    dim3 g;
+    RCCHK(coeff_grid((u64)bpr * batch * towers * 256, &g, "batch too large for one launch"));
+    hipLaunchKernelGGL(k_bv_inner, g, dim3(256), 0, pick(stream), A, bpr);
     return post_launch();
 }

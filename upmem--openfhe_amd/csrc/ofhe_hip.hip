@@ -16,7 +16,7 @@
 #include <new>
 #include <thread>
 
-#include "internal.hpp"
+#include "compose.hpp"
 #include "bconv_cols.hpp"
 
 using namespace ofhe;
@@ -1035,9 +1035,7 @@ int ofhe_hip_bconv_create_ex(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, ui
         }
     for (u32 j = 0; j < size_p; j++) {
         pv[j] = p[j];
-        const u128 mu = (~(u128)0) / p[j];  // floor(2^128 / p), p odd
-        pmu[2 * j] = (u64)mu;
-        pmu[2 * j + 1] = (u64)(mu >> 64);
+        barrett128(p[j], pmu + 2 * j);
         limb_red_consts(p[j], pred_of(qhlimb, qrows, ppad) + 3 * j);
     }
     // the matrix-core kernel's table (bconv_mma.hpp), appended 16-byte aligned
@@ -1052,16 +1050,10 @@ int ofhe_hip_bconv_create_ex(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, ui
             std::memcpy(h.data() + mm_off, tab.data(), tab.size());
         }
     }
-    const size_t words_all = h.size();
-    ofhe_bconv_s* b = new (std::nothrow) ofhe_bconv_s();
-    if (!b) return fail(OFHE_ERR_NOMEM, "bconv allocation failed");
+    ofhe_bconv_s* b = nullptr;
+    RCCHK(create_with_table(&b, &ofhe_bconv_s::d_mem, h, ctx->device, "bconv allocation failed", "bconv upload"));
     b->ctx = ctx;
     b->bcols = !opt.separate_cols;
-    const int rc = alloc_upload(&b->d_mem, h.data(), words_all * sizeof(u64), "bconv upload", ctx->device);
-    if (rc != OFHE_OK) {
-        delete b;
-        return rc;
-    }
     BconvArgs& A = b->args;
     A.qv = b->d_mem;
     A.qhinv = A.qv + size_q;
