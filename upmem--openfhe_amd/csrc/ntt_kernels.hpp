@@ -24,7 +24,13 @@
 //   k_block : the last 12 (8 at N = 2^16) stages on contiguous 4096-element
 //             blocks (34 KiB of LDS per workgroup): rounds of 4 radix-2
 //             stages held in registers (16 values per thread), padded LDS
-//             exchanges between rounds (see lds_pad()).
+//             exchanges between rounds (see lds_pad()).  With 8 stages
+//             (NR = 2) every exchange stays inside a 16-lane team that owns
+//             one 256-element group, and a workgroup covers 1024 elements of
+//             four consecutive polynomials of the batch: the four teams of a
+//             wave run the same group of the four polynomials, so they share
+//             every twiddle (stages 9-12: scalar loads) and no block barrier
+//             is needed (see block_body()).
 //   The metric pipeline runs column pass (fwd) -> k_block (fwd + Hadamard +
 //   inverse) -> column pass (inv): the Hadamard and the block stages of both
 //   directions share one residency.
@@ -529,18 +535,33 @@ constexpr u32 LDS_WORDS = 4096 + 4096 / 16;
 // the 1024 consecutive elements [1024w, 1024w + 1024).  From a thread's
 // round-3 LDS reads until the next block barrier no other wave touches that
 // region, so a wave can turn its lane-strided (128 B per lane) global accesses
-// into contiguous ones through it without a block barrier: instruction k,
-// lane i moves elements 128k + 2i and 128k + 2i + 1 of the wave's range.
+// into contiguous ones through it without a block barrier.
+//   TEAM = false (NR = 3): the wave's 1024 elements are consecutive words of
+//     one polynomial at wsrc: instruction k, lane i moves elements 128k + 2i
+//     and 128k + 2i + 1 of the wave's range.
+//   TEAM = true (NR = 2): each 16-lane team's 256 elements are one group of
+//     its own polynomial, at the per-lane pointer wsrc: instruction k, lane r
+//     of the team moves elements 32k + 2r and 32k + 2r + 1 of the group
+//     (256 contiguous bytes per team and instruction).
 // LDS processes one wave's operations in order; wave_barrier keeps the
 // compiler from reordering them across lanes.
+template <bool TEAM>
+struct StageMap {
+    u32 l, base;  // lane within the piece, first element of the thread's piece set
+    static constexpr u32 E = TEAM ? 32 : 128;  // elements per piece
+    __device__ __forceinline__ explicit StageMap(u32 tid)
+        : l(TEAM ? (tid & 15) : (tid & 63)), base(TEAM ? (tid >> 4) * 256 : (tid >> 6) * 1024) {}
+    __device__ __forceinline__ u32 g(int k) const { return E * k + 2 * l; }  // offset from wsrc; even
+    __device__ __forceinline__ u32 p(int k) const { return lds_pad(base + g(k)); }  // p, p + 1 share a 16-group
+};
+template <bool TEAM>
 __device__ __forceinline__ void wave_stage_in(const u64* wsrc, u64* lds, u32 tid, u64 (&out)[16]) {
-    const u32 lane = tid & 63, base = (tid >> 6) * 1024;
+    const StageMap<TEAM> m(tid);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const u64x2 v = ld2_s(wsrc + 128 * k + 2 * lane);
-        const u32 p = base + 128 * k + 2 * lane;  // even: p, p + 1 share a 16-group
-        lds[lds_pad(p)] = v.x;
-        lds[lds_pad(p) + 1] = v.y;
+        const u64x2 v = ld2_s(wsrc + m.g(k));
+        lds[m.p(k)] = v.x;
+        lds[m.p(k) + 1] = v.y;
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -549,34 +570,37 @@ __device__ __forceinline__ void wave_stage_in(const u64* wsrc, u64* lds, u32 tid
 }
 // wave_stage_in whose first NPRE 16-byte loads were issued earlier (pre[]),
 // so their HBM latency overlaps the caller's compute
-template <int NPRE>
+template <bool TEAM, int NPRE>
 __device__ __forceinline__ void wave_stage_in_pre(const u64* wsrc, u64* lds, u32 tid, const u64x2 (&pre)[NPRE > 0 ? NPRE : 1],
                                                   u64 (&out)[16]) {
-    const u32 lane = tid & 63, base = (tid >> 6) * 1024;
+    const StageMap<TEAM> m(tid);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const u64x2 v = k < NPRE ? pre[k < NPRE ? k : 0] : ld2_s(wsrc + 128 * k + 2 * lane);
-        const u32 p = base + 128 * k + 2 * lane;
-        lds[lds_pad(p)] = v.x;
-        lds[lds_pad(p) + 1] = v.y;
+        const u64x2 v = k < NPRE ? pre[k < NPRE ? k : 0] : ld2_s(wsrc + m.g(k));
+        lds[m.p(k)] = v.x;
+        lds[m.p(k) + 1] = v.y;
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int k = 0; k < 16; k++) out[k] = lds[tid * 17 + k];
     __builtin_amdgcn_wave_barrier();
 }
-__device__ __forceinline__ void wave_stage_out(const u64 (&v)[16], u64* lds, u32 tid, u64* wdst) {
-    const u32 lane = tid & 63, base = (tid >> 6) * 1024;
+// live = false (an empty team of a batch tail): the exchange runs, the stores do not
+template <bool TEAM>
+__device__ __forceinline__ void wave_stage_out(const u64 (&v)[16], u64* lds, u32 tid, u64* wdst, bool live = true) {
+    const StageMap<TEAM> m(tid);
 #pragma unroll
     for (int k = 0; k < 16; k++) lds[tid * 17 + k] = v[k];
     __builtin_amdgcn_wave_barrier();
+    u64x2 w[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const u32 p = base + 128 * k + 2 * lane;
-        u64x2 w;
-        w.x = lds[lds_pad(p)];
-        w.y = lds[lds_pad(p) + 1];
-        st2_s(wdst + 128 * k + 2 * lane, w);
+        w[k].x = lds[m.p(k)];
+        w[k].y = lds[m.p(k) + 1];
+    }
+    if (live) {  // one divergent region for the eight stores
+#pragma unroll
+        for (int k = 0; k < 8; k++) st2_s(wdst + m.g(k), w[k]);
     }
 }
 
@@ -595,29 +619,72 @@ __device__ __forceinline__ void wave_stage_out(const u64 (&v)[16], u64* lds, u32
 // stages of round 1 (strides 2048, 1024, 512), so the forward round 1 keeps
 // its last stage (stride 256) and the inverse round 1' its first (t = 256);
 // the inverse twist is the one of 512-element groups.
-// The body of k_block for work item wid (block g = wid % G of polynomial
-// tower pb = wid / G), on the caller's LDS (LDS_WORDS words).
+//
+// Work items.  NR = 3: item wid is the 4096-element block g = wid % G of
+// polynomial tower pb = wid / G (G = N / 4096); its sixteen 16-lane teams
+// h = tid >> 4 exchange through LDS across the workgroup.
+// NR = 2: a 256-element group is owned by one team and every exchange stays
+// inside it, so the teams of a wave need not belong to one polynomial.  The
+// four teams of a wave take the SAME group of four consecutive polynomials
+// b = 4 bq + team of one tower, and the four waves four adjacent groups
+// g = 4 (wid % G4) + wave of those polynomials (G4 = N / 1024, quad-tower
+// wid / G4 = t * ceil(batch / 4) + bq): the item still covers 4096
+// coefficients.  Nothing but the data depends on the polynomial, so
+//   * the round-2 twiddles (M0 = N/256 + g) are wave-uniform: scalar loads,
+//     SGPR operands, as dit_round3's;
+//   * every tw3 / DIT / twist line a wave requests serves four polynomials;
+//   * a wave reads only LDS slots it wrote: wave-level ordering replaces
+//     the block barriers.
+// A batch tail leaves one to three teams of the last quad empty: they load
+// the batch's last polynomial (clamped index), run every exchange, and
+// store nothing.
+// On the caller's LDS (LDS_WORDS words).
+template <int NR>
+__device__ __forceinline__ void block_sync() {
+    if (NR == 2)
+        __builtin_amdgcn_wave_barrier();  // in-wave exchange: LDS runs one wave's operations in order
+    else
+        __syncthreads();
+}
 template <int MODE, bool SPQ, int NR, int SK = 0>
 __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u64* dst, const u64* __restrict__ bdat,
                                            u32 batch, u32 wid, u64* lds, u32 tid) {
     static_assert(NR == 2 || NR == 3, "k_block covers the last 8 (NR=2) or 12 (NR=3) stages");
     static_assert(SK == 0 || (SK == 3 && NR == 3), "k_block: SK = 3 needs NR = 3");
+    constexpr bool TEAM = NR == 2;
     const u32 logn = P.log_n;
     const u32 N = 1u << logn;
-    const u32 G = N >> 12;  // blocks per polynomial
-    const u32 g = wid % G;
-    const u32 pb = wid / G;
-    const u32 t = pb / batch, b = pb % batch;
-    const u64 inner = (u64)t * N + ((u64)g << 12);
+    const u32 h = tid >> 4, r = tid & 15;
+    u32 g, t, b;       // g: 4096-element block (NR = 3) or 256-element group (NR = 2) of the polynomial
+    bool live = true;  // false: an empty team of the batch tail
+    if (TEAM) {
+        const u32 G4 = N >> 10, nq = (batch + 3) >> 2;
+        const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        g = (wid % G4) * 4 + wave;
+        const u32 pq = wid / G4;
+        t = pq / nq;
+        const u32 bt = (pq % nq) * 4 + (h & 3);
+        live = bt < batch;
+        b = live ? bt : batch - 1;
+    } else {
+        const u32 G = N >> 12;
+        g = wid % G;
+        const u32 pb = wid / G;
+        t = pb / batch;
+        b = pb % batch;
+    }
+    const u64 inner = (u64)t * N + ((u64)g << (TEAM ? 8 : 12));
     const u64 off = (u64)b * P.dstride + inner;
     const u64 boff = (u64)b * P.bstride + inner;
+    // the words wave_stage_* moves for this thread: its wave's 1024 (NR = 3) or its team's 256 (NR = 2)
+    const u32 wq = TEAM ? 0 : (tid >> 6) * 1024;
     const u64* blk = src + (u64)b * P.sstride + inner;
     u64* oblk = dst + off;
+    const u32 e3 = (TEAM ? r : tid) * 16;  // the thread's 16 round-3 words, from blk / oblk
     const TowerConst tc = P.tc[t];
     const u64 q = tc.q;
     const auto M = load_mod<SPQ, (bool)OFHE_QA_BLK>(tc);
     const u64* tw = P.tw + (u64)t * N * 2;
-    const u32 h = tid >> 4, r = tid & 15;
     // padded LDS bases (lds_pad(p) = p + p/16) of the three round layouts
     const u32 L1 = tid + h;      // lds_pad(tid + 256 k)      = L1 + 272 k
     const u32 L2 = h * 272 + r;  // lds_pad(256 h + r + 16 k) = L2 + 17 k
@@ -641,13 +708,14 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             for (int k = 0; k < 16; k++) v[k] = lds[L2 + 17 * k];
         } else {
 #pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = ld_s(blk + h * 256 + r + 16 * k);
+            for (int k = 0; k < 16; k++) v[k] = ld_s(blk + r + 16 * k);
         }
-        fwd_round16(v, tw, (N >> 8) + g * 16 + h, M);
+        // NR = 2: g is the group and wave-uniform, so these are scalar loads
+        fwd_round16(v, tw, (N >> 8) + (TEAM ? g : g * 16 + h), M);
 #pragma unroll
         for (int k = 0; k < 16; k++) lds[L2 + 17 * k] = v[k];
-        __syncthreads();
-        // round 3: st = 1, p = 16 tid + k
+        block_sync<NR>();
+        // round 3: st = 1, p = 16 tid + k (NR = 2: words 16 r + k of the team's group)
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = lds[L3 + k];
         // the second operand (the fused pipeline's Hadamard b, ModDown's x):
@@ -657,16 +725,16 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
         constexpr int BPF = ((MODE == MODE_FUSED && OFHE_COAL_B) || MODE == MODE_FWD_SUB) ? OFHE_B_PF : 0;
         u64x2 bpre[BPF > 0 ? BPF : 1];
 #pragma unroll
-        for (int k = 0; k < BPF; k++) bpre[k] = ld2_s(bdat + boff + (tid >> 6) * 1024 + 128 * k + 2 * (tid & 63));
+        for (int k = 0; k < BPF; k++) bpre[k] = ld2_s(bdat + boff + wq + StageMap<TEAM>(tid).g(k));
         if (OFHE_TW3) {
             const u64* tw3 = P.tw3 + (u64)t * (N / 16) * 30;
-            const u32 U = N >> 4, u = g * 256 + tid;
+            const u32 U = N >> 4, u = TEAM ? g * 16 + r : g * 256 + tid;
             fwd_stage16_t3<0>(v, tw3, U, u, M);
             fwd_stage16_t3<1>(v, tw3, U, u, M);
             fwd_stage16_t3<2>(v, tw3, U, u, M);
             fwd_stage16_t3<3>(v, tw3, U, u, M);
         } else {
-            fwd_round16(v, tw, (N >> 4) + g * 256 + tid, M);
+            fwd_round16(v, tw, (N >> 4) + (TEAM ? g * 16 + r : g * 256 + tid), M);
         }
         if (!(MODE == MODE_FUSED && kMontFused) && MODE != MODE_FWD_SUB) {
 #pragma unroll
@@ -682,28 +750,28 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             // canonicalisation gives the same residue as ModSubFastEq followed
             // by ModMulFastConstEq (~10 instructions per coefficient fewer)
             u64 xx[16];
-            wave_stage_in_pre<BPF>(bdat + boff + (tid >> 6) * 1024, lds, tid, bpre, xx);
+            wave_stage_in_pre<TEAM, BPF>(bdat + boff + wq, lds, tid, bpre, xx);
             const u64 sc = P.scal[3 * t + 1], scp = P.scal[3 * t + 2];
             const u64 q12 = M.q8 + M.q4;
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = canon4m(shoup_lazy(xx[k] + q12 - v[k], sc, scp, M), M);
-            wave_stage_out(v, lds, tid, oblk + (tid >> 6) * 1024);
+            wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
             return;
         }
         if (MODE == MODE_FWD) {
             if (OFHE_COAL) {
-                wave_stage_out(v, lds, tid, oblk + (tid >> 6) * 1024);
+                wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
             } else {
-                ulonglong2* o = reinterpret_cast<ulonglong2*>(oblk + tid * 16);
+                ulonglong2* o = reinterpret_cast<ulonglong2*>(oblk + e3);
 #pragma unroll
-                for (int k = 0; k < 8; k++) o[k] = make_ulonglong2(v[2 * k], v[2 * k + 1]);
+                for (int k = 0; k < 8 && live; k++) o[k] = make_ulonglong2(v[2 * k], v[2 * k + 1]);
             }
             return;
         }
         // Hadamard with b (evaluation form), NativeVectorT::ModMulNoCheckEq
         if (OFHE_COAL_B) {
             u64 bb[16];
-            wave_stage_in_pre<BPF>(bdat + boff + (tid >> 6) * 1024, lds, tid, bpre, bb);
+            wave_stage_in_pre<TEAM, BPF>(bdat + boff + wq, lds, tid, bpre, bb);
             if (kMontFused) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) v[k] = mont_mul(v[k], bb[k], q, tc.qinv);  // (0, 2q)
@@ -712,7 +780,7 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
                 for (int k = 0; k < 16; k++) v[k] = barrett_ref(v[k], bb[k], q, tc.mu, tc.nshift);
             }
         } else {
-            const ulonglong2* bp = reinterpret_cast<const ulonglong2*>(bdat + boff + tid * 16);
+            const ulonglong2* bp = reinterpret_cast<const ulonglong2*>(bdat + boff + e3);
 #pragma unroll
             for (int k = 0; k < 8; k++) {
 #ifdef OFHE_ABL_NOB
@@ -727,9 +795,9 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
         // no barrier: round 3' below rewrites only this thread's own LDS slots
     } else {
         if (OFHE_COAL) {
-            wave_stage_in(blk + (tid >> 6) * 1024, lds, tid, v);
+            wave_stage_in<TEAM>(blk + wq, lds, tid, v);
         } else {
-            const ulonglong2* ip = reinterpret_cast<const ulonglong2*>(blk + tid * 16);
+            const ulonglong2* ip = reinterpret_cast<const ulonglong2*>(blk + e3);
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 ulonglong2 a = ip[k];
@@ -747,18 +815,22 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
     dit_round3(v, dtw, M);
 #pragma unroll
     for (int k = 0; k < 16; k++) lds[L3 + k] = v[k];
-    __syncthreads();
+    block_sync<NR>();
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = lds[L2 + 17 * k];
     dit_round16(v, dtw, 16, r, M);
-    const u64* tw_ = P.twist + (u64)t * N * 2 + 2 * ((u64)g << 12);
+    const u64* tw_ = P.twist + (u64)t * N * 2 + 2 * ((u64)g << (TEAM ? 8 : 12));
     if (NR == 2) {
-        // twist into the GS column pass's input, lazy [0, 4q)
+        // twist into the GS column pass's input, lazy [0, 4q); the same
+        // twist entries for the wave's four polynomials
 #pragma unroll
         for (int k = 0; k < 16; k++) {
-            const u32 p = h * 256 + r + 16 * k;
-            const Tw f = ldtw(tw_, p);
-            st_s(oblk + p, shoup_lazy(v[k], f.w, f.wp, M));
+            const Tw f = ldtw(tw_, r + 16 * k);
+            v[k] = shoup_lazy(v[k], f.w, f.wp, M);
+        }
+        if (live) {  // one divergent region for the sixteen stores
+#pragma unroll
+            for (int k = 0; k < 16; k++) st_s(oblk + r + 16 * k, v[k]);
         }
         return;
     }

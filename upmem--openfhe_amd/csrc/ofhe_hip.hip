@@ -587,9 +587,13 @@ static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, con
 template <int MODE>
 static void launch_block(const PlanArgs& a, bool spq, const u64* src, u64* dst, const u64* b, u32 batch,
                          hipStream_t s, int split = SPLIT_COLS) {
-    const u32 nwg = batch * a.towers * (1u << (a.log_n - 12));
     with_bool(spq, [&](auto sp) { with_int<8, 9, 12>((int)block_stages(split, a.log_n), [&](auto st) {
         constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
+        // one work item per 4096-element block (NR = 3), or per 1024 elements
+        // of four consecutive polynomials of a tower (NR = 2, block_body): the
+        // same count when batch % 4 == 0
+        const u32 nwg = NR == 2 ? ((batch + 3) / 4) * a.towers * (1u << (a.log_n - 10))
+                                : batch * a.towers * (1u << (a.log_n - 12));
         hipLaunchKernelGGL((k_block<MODE, decltype(sp)::value, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b,
                            batch, nwg);
     }); });
