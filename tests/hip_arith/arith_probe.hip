@@ -171,7 +171,7 @@ struct Entry {
 #define E(name, ...) {name, __VA_ARGS__::IN, __VA_ARGS__::OUT, &launch<__VA_ARGS__>}
 static const Entry kTable[] = {
     E("mulhi_approx", HMulhiApprox<false>),
-    E("mulhi_approx_qa", HMulhiApprox<true>),  // not on the shipped path (OFHE_QA_* = 0)
+    E("mulhi_approx_qa", HMulhiApprox<true>),  // not on the shipped path (every kernel uses Mod<SPQ, false>)
     E("mulhi_exact", HMulhiExact),
     E("mul128", HMul128),
     E("csub", HCsub),
@@ -200,7 +200,7 @@ static const Entry kTable[] = {
     E("gs_bfly_spq", HGsBfly<true>),
     E("barrett_ref", HBarrettRef),
     E("mont_mul", HMont<false>),
-    E("mont_mul2", HMont<true>),  // not on the shipped path (OFHE_MONT2 = 0)
+    E("mont_mul2", HMont<true>),  // not on the shipped path (mont_mul is the one kernels call)
     E("barrett128", HBarrett128),
     E("switch_mod1", HSwitchMod),
     E("bm_reduce", HBmReduce<false, false, false>),

@@ -1,8 +1,8 @@
 """Worst-case range checks of the lazy reductions in the column passes (CPU).
 
 The GPU kernels keep residues in redundant ranges between butterfly stages
-(csrc/ntt_kernels.hpp: gs_bfly_b / inv_stage16_b, OFHE_LAZY_GS; ct_bfly_cs,
-OFHE_LAZY_FWD).  These tests replay the exact compile-time schedule of those
+(csrc/ntt_kernels.hpp: gs_bfly_b / inv_stage16_b / cols_inv_b for the inverse;
+ct_bfly_cs for the forward).  These tests replay the exact compile-time schedule of those
 kernels on the largest representative of every residue each step may produce
 and check (1) no intermediate reaches 2^64 and (2) the final canonicalisation
 returns the residue.  Parity of the kernels themselves is checked on the GPU
@@ -79,7 +79,7 @@ def test_lazy_gs_two_rounds(q):
 
 @pytest.mark.parametrize("q", [(1 << 60) - (1 << 17) + 1, (1 << 59) + 1])
 def test_lazy_ct_alternating(q):
-    """ct_bfly_cs with OFHE_LAZY_FWD: CS stages subtract 8q, outputs stay < 16q"""
+    """ct_bfly_cs, alternating schedule: CS stages subtract 8q, outputs stay < 16q"""
     rng = random.Random(q ^ 1)
     for _ in range(200):
         v = [_worst(rng.randrange(q), q, 12 * q) for _ in range(16)]  # column-pass output < 12q
@@ -100,7 +100,7 @@ def test_lazy_ct_alternating(q):
 
 @pytest.mark.parametrize("q", [(1 << 60) - (1 << 17) + 1, (1 << 59) + 1])
 def test_fwd_first_round_canonical_input(q):
-    """fwd_round16_canon (OFHE_FWD_CANON): inputs < 4q, no conditional subtract
+    """fwd_round16_canon: inputs < 4q, no conditional subtract
     before the round's last stage, output < 12q like every other round"""
     rng = random.Random(q ^ 2)
     for _ in range(200):

@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Is the gfx950 device code of two csrc directories the same, kernel by kernel?
+
+    python tools/isa_diff.py PARENT_CSRC upmem--openfhe_amd/csrc
+
+Each translation unit of the Makefile's SRCS is compiled device-only to
+assembly (the Makefile's `asm` flags) in both trees; each directory must sit in
+its tree (the sources include ../../include/ofhe_hip.h).  The assembly is cut
+at function symbols, and every kernel's text -- instructions, its .amdhsa_kernel
+descriptor, and its entry of the amdhsa.kernels metadata (registers, LDS,
+scratch, argument layout) -- is compared by mangled name.  Local labels carry
+the function's ordinal in the file, which a deleted kernel shifts, so the
+ordinal is dropped; so are the __hip_cuid_ lines, a hash of the source text.
+What lies outside any function is compared as "(file scope)".  Exit status 1
+when a kernel differs or exists only in the second tree.
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+MAKEFILE = os.path.join(HERE, "..", "upmem--openfhe_amd", "csrc", "Makefile")
+BEGIN = re.compile(r"; -- Begin function (\S+)")  # on the symbol's .globl or .weak line
+OBJECT = re.compile(r"^\s*\.type\s+\S+,@object")
+ORDINAL =re.compile(r"(\.L(?:BB|func_(?:begin|end)|JTI|tmp|CPI))\d+")
+
+
+def make_var(name, default=None):
+    m = re.search(rf"^{name}\s*[:?]?=\s*(.*)$", open(MAKEFILE).read(), re.M)
+    return m.group(1).strip() if m else default
+
+
+def assembly(csrc, src):
+    arch = make_var("ARCH")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "tu.s")
+        subprocess.run([make_var("HIPCC"), "-O3", "-std=c++17", f"--offload-arch={arch}", "--cuda-device-only", "-S",
+                        "-o", out, src], cwd=csrc, check=True, stderr=subprocess.DEVNULL)
+        return open(out).read()
+
+
+def kernels(text):
+    """{mangled name: text} of one assembly file, plus "(file scope)"."""
+    text, _, meta = text.partition("amdhsa.kernels:\n")
+    parts, name = {"(file scope)": []}, "(file scope)"
+    for line in text.splitlines():
+        if "__hip_cuid_" in line:
+            continue
+        m = BEGIN.search(line)
+        if m:
+            name = m.group(1)
+            parts[name] = []
+        elif OBJECT.match(line):  # data objects follow the functions
+            name = "(file scope)"
+        parts[name].append(ORDINAL.sub(r"\1", line))
+    for entry in re.split(r"^  - ", meta, flags=re.M)[1:]:
+        m = re.search(r"^\s*\.name:\s*(\S+)", entry, re.M)
+        if m:
+            parts.setdefault(m.group(1), []).append(entry)
+    return {k: "\n".join(v) for k, v in parts.items()}
+
+
+def main(a, b):
+    srcs = make_var("SRCS").split()
+    with ThreadPoolExecutor(os.cpu_count() or 1) as pool:
+        texts = list(pool.map(lambda job: assembly(*job), [(d, s) for s in srcs for d in (a, b)]))
+    bad = 0
+    for i, src in enumerate(srcs):
+        ka, kb = kernels(texts[2 * i]), kernels(texts[2 * i + 1])
+        only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
+        differ = sorted(k for k in set(ka) & set(kb) if ka[k] != kb[k])
+        print(f"{src}: {len(ka) - 1} and {len(kb) - 1} functions; with the file scope "
+              f"{len(set(ka) & set(kb)) - len(differ)} identical, "
+              f"{len(differ)} differ, {len(only_a)} only in the first tree, {len(only_b)} only in the second")
+        for tag, names in (("differs", differ), ("only in first", only_a), ("only in second", only_b)):
+            for k in names:
+                print(f"  {tag}: {k}")
+        bad += len(differ) + len(only_b)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])))

@@ -78,11 +78,7 @@ __device__ __forceinline__ u64 switch_mod1(u64 v, const SwMod& m) {
 // subb_co, 2 cndmask on that vcc: 4 ops, no 64-bit compare, fewer VCC
 // hazard nops).  m MUST be uniform across the wave: an "s" operand of a
 // divergent value would be read from lane 0.
-#ifndef OFHE_CSUB_ASM
-#define OFHE_CSUB_ASM 1
-#endif
 __device__ __forceinline__ u64 csub_s(u64 x, u64 m) {
-#if OFHE_CSUB_ASM
     u32 lo, hi;
     asm("v_subrev_co_u32 %0, vcc, %4, %2\n\t"
         "v_subbrev_co_u32 %1, vcc, %5, %3, vcc\n\t"
@@ -92,24 +88,12 @@ __device__ __forceinline__ u64 csub_s(u64 x, u64 m) {
         : "v"(lo32(x)), "v"(hi32(x)), "s"(lo32(m)), "v"(hi32(m))
         : "vcc");
     return pack(lo, hi);
-#else
-    return csub(x, m);
-#endif
 }
 
 // floor(a*b / 2^64) - e, e in {0, 1, 2}: drops a0*b0 and the carry of the
-// middle sum.
-#ifndef OFHE_QH_ADDC
-#define OFHE_QH_ADDC 0  // measured: more instructions (add_co + cndmask), kept for reference
-#endif
-#ifndef OFHE_QH_MAD1
-#define OFHE_QH_MAD1 0  // 1: the quotient's second middle word added by a multiply-add by an opaque 1 (A/B: no gain)
-#endif
-// `one` is 1 held in an SGPR the compiler cannot see through (Mod::one, loaded
-// from the tower constants by the kernels' load_mod): then hi32(m2) * one + acc is ONE v_mad_u64_u32,
-// where the plain 64-bit add of two zero-extended words costs a v_mov_b32 (the
-// zero high word) plus a v_lshl_add_u64.  With a literal 1 LLVM folds the
-// multiply away and the add comes back.
+// middle sum.  `one` (Mod::one, TowerConst::one: a 1 the compiler cannot see
+// through) fed a multiply-add that replaced the final 64-bit add; that form
+// gained nothing and is gone, the argument is read by no path.
 template <bool QA = false>
 __device__ __forceinline__ u64 mulhi_approx(u64 a, u64 b, u32 one = 1) {
     if (QA) {
@@ -128,18 +112,8 @@ __device__ __forceinline__ u64 mulhi_approx(u64 a, u64 b, u32 one = 1) {
         asm("" : "+v"(sc));
         return mad32(hi32(a), hi32(b), sc);
     }
-    if (OFHE_QH_ADDC) {
-        // the two middle high words summed with an explicit carry word, so the
-        // 64-bit accumulator is built by add/carry instead of zero-extending
-        // moves plus a 64-bit add
-        const u32 h1 = __umulhi(lo32(a), hi32(b));
-        const u32 h2 = __umulhi(hi32(a), lo32(b));
-        const u32 s = h1 + h2;
-        return mad32(hi32(a), hi32(b), pack(s, s < h1));
-    }
     const u64 m1 = mad32(lo32(a), hi32(b), 0);
     const u64 m2 = mad32(hi32(a), lo32(b), 0);
-    if (OFHE_QH_MAD1) return mad32(hi32(m2), one, mad32(hi32(a), hi32(b), m1 >> 32));
     return mad32(hi32(a), hi32(b), (m1 >> 32) + (m2 >> 32));
 }
 
@@ -159,8 +133,8 @@ __device__ __forceinline__ u64 mulhi_exact(u64 a, u64 b) {
 // instead of a multiply.  Every modulus chain OpenFHE builds with
 // FirstPrime/PreviousPrime near 2^L (nbtheory-impl.h:334-379) has this form.
 // QA: the Shoup quotient's two middle words summed by add_co/addc into the
-// final mad's accumulator pair (mulhi_approx<true>); chosen per kernel where a
-// same-process A/B measured it faster (OFHE_QA_* in ntt_kernels.hpp)
+// final mad's accumulator pair (mulhi_approx<true>); no kernel selects it (a
+// same-process A/B per kernel found none faster), the device probe tests it
 template <bool SPQ, bool QA = false>
 struct Mod {
     u64 q;    // modulus, q < 2^60
@@ -170,7 +144,7 @@ struct Mod {
     u64 nq4;  // 2^64 - 4q
     u64 nq8;  // 2^64 - 8q
     u32 sh;   // L - 32 (SPQ only)
-    u32 one = 1;  // 1; loaded from TowerConst (opaque to LLVM) in the NTT kernels, see mulhi_approx
+    u32 one = 1;  // 1; loaded from TowerConst (opaque to LLVM) in the NTT kernels; unread, see mulhi_approx
 };
 
 // Shoup with precomputed wp = floor(w*2^64/q): a*w mod q in [0, 4q) for any
@@ -190,9 +164,6 @@ __device__ __forceinline__ u64 shoup_lazy(u64 a, u64 w, u64 wp, const Mod<SPQ, Q
     return pack(lo32(s), hi);
 }
 
-#ifndef OFHE_ACC_PIN
-#define OFHE_ACC_PIN 1
-#endif
 // acc + shoup_lazy(a, w, wp) mod 2^64 with acc folded into the first
 // multiply-add of the remainder: the Cooley-Tukey butterfly's x + w y costs no
 // separate 64-bit add (the true value acc + [0, 4q) is below 2^64 at every
@@ -201,9 +172,7 @@ template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 shoup_lazy_acc(u64 a, u64 w, u64 wp, const Mod<SPQ, QA>& M, u64 acc) {
     const u64 qh = mulhi_approx<QA>(a, wp, M.one);
     u64 s = mad32(lo32(a), lo32(w), acc);
-#if OFHE_ACC_PIN
     asm("" : "+v"(s));  // keeps LLVM from re-associating acc out of the mad chain
-#endif
     s = mad32(lo32(qh), lo32(M.nq), s);
     u32 hi;
     if (SPQ)
@@ -267,16 +236,13 @@ __device__ __forceinline__ u64 barrett_ref(u64 a, u64 b, u64 q, u64 mu, u32 n_sh
 //   gives (0, 2q) with no carry/borrow test on the low word.
 // qinv = q^-1 mod 2^64.
 //
-// OFHE_MONT2: the same value with the carries taken by add_co/addc instead
-// of zero-extended 64-bit adds (LLVM emitted 9 register moves per product for
-// the form below):
+// mont_mul2 (no kernel calls it; the device probe tests it): the same value
+// with the carries taken by add_co/addc instead of zero-extended 64-bit adds
+// (LLVM emitted 9 register moves per product for mont_mul's form):
 //   u = a1 b0 + a0 b1 (< 2^64 under the same bounds), t1 = x1 + u0 with
 //   carry c, hi64(t) = a1 b1 + (u1 + c);
 //   hi64(m q) = m1 q1 + hi32(S1) + L1 + carry(lo32(S1) + L0) with
 //   S1 = m1 q0 + hi32(m0 q0) < 2^64 and L = m0 q1 < 2^60 (q < 2^60).
-#ifndef OFHE_MONT2
-#define OFHE_MONT2 0
-#endif
 __device__ __forceinline__ u64 mont_mul2(u64 a, u64 b, u64 q, u64 qinv) {
     const u64 x = mad32(lo32(a), lo32(b), 0);
     const u64 u = mad32(hi32(a), lo32(b), mad32(lo32(a), hi32(b), 0));
@@ -305,7 +271,6 @@ __device__ __forceinline__ u64 mont_mul2(u64 a, u64 b, u64 q, u64 qinv) {
     return tq - h + (u64)e;
 }
 __device__ __forceinline__ u64 mont_mul(u64 a, u64 b, u64 q, u64 qinv) {
-    if (OFHE_MONT2) return mont_mul2(a, b, q, qinv);
     const u64 x = mad32(lo32(a), lo32(b), 0);
     const u64 y = mad32(hi32(a), lo32(b), x >> 32);  // < 1.5*2^63 + 2^32
     const u64 z = mad32(lo32(a), hi32(b), y);        // + < 2^60: no wrap

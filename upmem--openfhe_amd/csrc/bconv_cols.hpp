@@ -27,9 +27,6 @@
 
 namespace ofhe {
 
-#ifndef OFHE_BCC_STAGE_BAR
-#define OFHE_BCC_STAGE_BAR 1  // scheduling barrier between the column stages (A/B)
-#endif
 #ifndef OFHE_BCC_MINW
 #define OFHE_BCC_MINW 3  // waves per SIMD the register budget is sized for
 #endif
@@ -57,7 +54,7 @@ __device__ __forceinline__ void bcc_icol_source(const PlanArgs& P, const BmSrc* 
     constexpr u32 N = 1u << 17, COLS = N / BC_ROWS;
     const u32 col = lane & 15, qq = lane >> 4;
     const u32 ts = src_rel + src;
-    const auto M = load_mod<SPQ, (bool)OFHE_QA_CI>(P.tc[ts]);
+    const Mod<SPQ> M = load_mod<SPQ>(P.tc[ts]);
     const u64* itw = P.itw + (u64)ts * N * 2;
     const u64* xs = xb + (u64)src * N + col;
     u64 v[8];
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(BC_THREADS, OFHE_BCC_MINW) void k_bconv_cols(BconvA
     auto colpass = [&](u64(&vv)[16], u32 j) {
         if (j >= A.size_p) return;  // the partner lane (c ^ 16) has the same h
         const u32 jo = j >= A.gap_at ? j + A.gap : j;
-        const auto M = load_mod<SPQ, (bool)OFHE_QA_BCC>(P.tc[jo]);
+        const Mod<SPQ> M = load_mod<SPQ>(P.tc[jo]);
         const u64* tw = P.tw + (u64)jo * N * 2;
         // stages s = 0..3 (row distance 16 >> s, g distance 8 >> s); CS at s = 0, 2
 #pragma unroll
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(BC_THREADS, OFHE_BCC_MINW) void k_bconv_cols(BconvA
 #pragma unroll
                 for (int g = jb * 2 * hg; g < jb * 2 * hg + hg; g++) ct_bfly_cs(vv[g], vv[g + hg], tw_, M, (s & 1) == 0);
             }
-            if (OFHE_BCC_STAGE_BAR) __builtin_amdgcn_sched_barrier(0);  // one stage's twiddles in flight
+            __builtin_amdgcn_sched_barrier(0);  // one stage's twiddles in flight
         }
         // stage s = 4: rows (2g, 2g + 1) = lanes (c, c ^ 16); par 0 keeps g < 8, par 1 g >= 8
         u64* oj = ob + (u64)jo * N;

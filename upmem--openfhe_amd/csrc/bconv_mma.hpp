@@ -45,15 +45,6 @@ constexpr u64 DIGIT_BIAS = 0x8080808080808080ull;
 constexpr u32 BCONV_MMA_QMAX = 64;            // size_q <= 64: |C| <= 2^23 (K-steps up to 16)
 constexpr u32 BCONV_MMA_LDS_MAX = 64 * 1024;  // one target chunk's fragments + constants (dynamic LDS)
 constexpr u32 BCONV_MMA_THREADS = 512;
-#ifndef OFHE_BCONV_MMA
-#define OFHE_BCONV_MMA 1  // 0: the limb / 128-bit kernels only (A/B builds)
-#endif
-#ifndef OFHE_BCONV_MMA_SPQ
-#define OFHE_BCONV_MMA_SPQ 1  // special-prime reduction when every target allows it
-#endif
-#ifndef OFHE_BCONV_MMA_PF
-#define OFHE_BCONV_MMA_PF 1  // prefetch the next group's x (K-steps <= 8)
-#endif
 #ifndef OFHE_BCONV_MMA_WAVES
 #define OFHE_BCONV_MMA_WAVES 0  // __launch_bounds__ min waves per SIMD (0: compiler's choice)
 #endif
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(BCONV_MMA_THREADS, OFHE_BCONV_MMA_WAVES) void k_bco
     BconvArgs A, const u64* __restrict__ x, u64* __restrict__ out, u32 batch) {
     OFHE_VGPR_FLOOR();
     constexpr bool WIDE = KS > 8;
-    constexpr bool PF = OFHE_BCONV_MMA_PF && KS <= 8;  // registers: the prefetch holds 2 KS words
+    constexpr bool PF = KS <= 8;  // prefetch the next group's x; registers: the prefetch holds 2 KS words
     extern __shared__ __attribute__((aligned(16))) unsigned char bm_lds[];
     const u32 tiles = A.mm_tiles, tpc = A.mm_tpc;
     const u32 t0 = blockIdx.y * tpc;

@@ -17,13 +17,6 @@
 
 using namespace ofhe;
 
-// 1: ScaleAndRound and ExpandCRTBasisQlHat of the three products as one launch
-// each (k_scale_round_lift); 0: as two (DESIGN.md "BFV multiplication
-// (HPSPOVERQLEVELED)" has the A/B)
-#ifndef OFHE_LEVELED_FUSED_LIFT
-#define OFHE_LEVELED_FUSED_LIFT 1
-#endif
-
 struct ofhe_bfv_level_s {
     ofhe_ctx_t ctx = nullptr;
     u32 l = 0, size_q = 0, log_n = 0;
@@ -201,16 +194,12 @@ int ofhe_hip_bfv_eval_mult_leveled(ofhe_bfv_level_t h, const uint64_t* c0, const
     RCCHK(tensor_and_intt(pqr, E, T, one, batch, stream));
     u64* outs[3] = {out0, out1, out2};
     for (int k = 0; k < 3; k++) {
-        // ScaleAndRound to Q_l (372-374), ExpandCRTBasisQlHat below the full level (376-380)
-        if (!dropped) {
+        // ScaleAndRound to Q_l (372-374), and below the full level ExpandCRTBasisQlHat (376-380)
+        // in the same launch (k_scale_round_lift)
+        if (!dropped)
             RCCHK(sr_run(h->sr, T + k * one, outs[k], batch, s));
-        } else if (OFHE_LEVELED_FUSED_LIFT) {
+        else
             RCCHK(sr_lift_run(h, T + k * one, outs[k], batch, s));
-        } else {
-            // the products' Q_l images go where the inputs' were (Cl holds two polynomials: one at a time)
-            RCCHK(sr_run(h->sr, T + k * one, Cl, batch, s));
-            RCCHK(ql_hat_run(h, Cl, nullptr, outs[k], batch, s));
-        }
     }
     return OFHE_OK;
 }

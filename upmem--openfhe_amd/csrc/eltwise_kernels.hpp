@@ -23,11 +23,7 @@ __device__ __forceinline__ u64 modsub_fast(u64 a, u64 b, u64 q) { return a < b ?
 // 16 towers, batch 256 on MI355X, a 4096-block grid-stride launch moved
 // 4.5-4.7 TB/s, the full grid 6.0-6.3 TB/s (ModMul best with 2 pairs per
 // thread, the add/sub/scalar ops with 1; DESIGN.md "Element-wise bandwidth").
-#ifdef OFHE_ELT_UNROLL
-__host__ __device__ constexpr int elt_unroll(int) { return OFHE_ELT_UNROLL; }
-#else
 __host__ __device__ constexpr int elt_unroll(int op) { return op == ELT_MUL ? 2 : 1; }
-#endif
 // LeveledSHEBase::EvalMultCore for two 2-element ciphertexts
 // (base-leveledshe.cpp:667-672): o2 = c1 d1, o1 = c1 d0 + c0 d1, o0 = d0 c0,
 // each product NativeVectorT::ModMul (Barrett, ubintnat.h:1399-1413) and the

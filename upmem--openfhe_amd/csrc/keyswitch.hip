@@ -22,26 +22,13 @@
 
 using namespace ofhe;
 
-// A/B switches (tools/exp_ks.py): KeySwitchCore reads each digit's own towers
-// from the ciphertext instead of a copy (OFHE_KS_OWN); ModUp transforms the
-// Q-after-digit and P towers in one launch at full level (OFHE_KS_MERGE).
-#ifndef OFHE_KS_OWN
-#define OFHE_KS_OWN 1
-#endif
-#ifndef OFHE_KS_MERGE
-#define OFHE_KS_MERGE 1
-#endif
-// KeySwitchCore's two ModDowns as one set of launches over 2 x batch
-// (mod_down_run, nout = 2) instead of two forked streams (OFHE_KS_MD2)
-#ifndef OFHE_KS_MD2
-#define OFHE_KS_MD2 1
-#endif
+// Tuning knob (tools/exp_ks.py):
 // side streams the ModUp digits are spread over (digit j on stream j mod n)
 #ifndef OFHE_KS_NSIDE
 #define OFHE_KS_NSIDE 2
 #endif
 constexpr int KS_NSIDE = OFHE_KS_NSIDE;
-static_assert(KS_NSIDE >= 2, "KeySwitchCore's two ModDowns use side streams 0 and 1");
+static_assert(KS_NSIDE >= 1, "ModUp spreads its digits over the side streams");
 
 namespace {
 
@@ -524,7 +511,7 @@ static int ks_precompute_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, const u
         RCCHK(bconv_run(B, slot + st * N, slot, batch_, s));
         // complement towers to evaluation form (394)
         RCCHK(plan_ntt_range(k->plan, false, 0, st, slot, slot, ds, ds, batch_, s));
-        if (OFHE_KS_MERGE && l == k->size_q) {
+        if (l == k->size_q) {
             // full level: the Q towers after the digit and the P towers are
             // adjacent both in the plan and in the slot -- one launch
             RCCHK(plan_ntt_range(k->plan, false, st + n, (u32)(l + P) - st - n, slot + (st + n) * N,
@@ -621,21 +608,14 @@ int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uin
     u64* c1 = ct.w() + (u64)batch * poly;
     // the inner product reads each digit's own towers straight from c (beta <= 4),
     // so the precompute skips copying them into the digit slots
-    const bool own_from_c = OFHE_KS_OWN && L->beta <= 4;
+    const bool own_from_c = L->beta <= 4;
     RCCHK(ks_precompute_impl(k, L, size_ql, c, dg.w(), batch, s, !own_from_c));
     RCCHK(ks_fast_core_ext_impl(k, L, size_ql, dg.w(), key_b, key_a, c0, c1, batch, s, own_from_c ? c : nullptr));
-    if (OFHE_KS_MD2) {
-        // both ModDowns in one set of launches (c1 = c0 + batch * poly)
-        ModDownArgs A;
-        RCCHK(ks_md_args(k, L, t, &A));
-        u64* const outs[2] = {out0, out1};
-        return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s);
-    }
-    KsFork fk;  // after dg, ct: joins before they are freed
-    RCCHK(fk.open(k, s));
-    RCCHK(ks_mod_down_impl(k, L, c0, out0, t, batch, fk.f[0]));
-    RCCHK(ks_mod_down_impl(k, L, c1, out1, t, batch, fk.f[1]));
-    return fk.join();
+    // both ModDowns in one set of launches over 2 x batch (c1 = c0 + batch * poly)
+    ModDownArgs A;
+    RCCHK(ks_md_args(k, L, t, &A));
+    u64* const outs[2] = {out0, out1};
+    return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1059,9 +1039,6 @@ int ofhe_hip_automorphism(ofhe_plan_t p, uint32_t k, int eval_form, const uint64
 //   (x + NTT(sw t)) a = (x - NTT(sw (-t))) a           (mod-reduce)
 // with the canonical residues of the reference's own order of operations.
 // ---------------------------------------------------------------------------
-#ifndef OFHE_RESCALE_FUSE
-#define OFHE_RESCALE_FUSE 1  // 0: k_switch_scale then the column pass (A/B)
-#endif
 // a scalar table of the plan, keyed by its own content
 static int plan_table(ofhe_plan_t p, const std::vector<u64>& words, const u64** out) {
     return cached_table(p->tab_mu, p->tabs, words, "rescale tables", out,
@@ -1131,7 +1108,7 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
     RCCHK(sy.alloc((size_t)batch * L * N * 8, s, p->ctx));
     RCCHK(plan_ntt_range(p, true, L, 1, x + (u64)L * N, sl.w(), xs, N, batch, s));
     const u64 ys = (u64)L * N;
-    if (log_n > 12 && p->split != SPLIT_T9 && OFHE_RESCALE_FUSE) {
+    if (log_n > 12 && p->split != SPLIT_T9) {
         // the lift happens in the column pass's loads (k_cols<.., SWS>): the
         // switched towers are never written to HBM before their transform
         RCCHK(plan_cols_switch(p, 0, L, sl.w(), N, ql, A.pre, dsw, sy.w(), ys, batch, s));
@@ -1218,7 +1195,7 @@ int ofhe_hip_bv_precompute(ofhe_plan_t p, uint32_t towers, const uint64_t* c, ui
     RCCHK(sc.alloc((size_t)batch * TN * 8, s, p->ctx));
     RCCHK(plan_ntt_range(p, true, 0, T, c, sc.w(), TN, TN, batch, s));
     const u64 dstride = (u64)T * TN;  // words per batch entry of digits
-    const bool fused = log_n > 12 && p->split != SPLIT_T9 && OFHE_RESCALE_FUSE;
+    const bool fused = log_n > 12 && p->split != SPLIT_T9;
     const u32 bpr = (u32)((N / 2 + 255) / 256);
     dim3 g;
     RCCHK(coeff_grid((u64)bpr * batch * T * 256, &g, "batch too large for one launch"));

@@ -11,9 +11,9 @@
 //   the same values, see dit_round3() below -- and its column-pass stages as
 //   the reference's GS.
 // Values stay lazily reduced between stages (forward and DIT in [0, 16q),
-// GS in [0, 8q) with compile-time bounds per register, OFHE_LAZY_GS) and are
-// made canonical on output, so results equal the
-// reference bit for bit (its outputs are the canonical residues).
+// GS in [0, 8q) with compile-time bounds per register, inv_round16_b) and are
+// made canonical on output, so results equal the reference bit for bit (its
+// outputs are the canonical residues).
 //
 // Decomposition for N = 2^logN >= 2^12 (one tower = 512 KiB at 2^16, more
 // than a CU's 160 KiB LDS):
@@ -52,33 +52,14 @@ struct TowerConst {
     u32 nshift;    // msb(q) - 2
     u32 spq_sh;    // msb(q) - 32 when q = 2^msb - d with d < 2^32, else 0
     u64 qinv;      // q^-1 mod 2^64 (Montgomery Hadamard)
-    u32 one;       // 1, loaded so LLVM cannot fold it (Mod::one, mulhi_approx)
+    u32 one;       // 1, loaded so LLVM cannot fold it (Mod::one); unread, see mulhi_approx
     u32 pad_;
 };
-// Shoup quotient form per kernel (Mod<SPQ, QA>, arith.hpp): add_co/addc into
-// the accumulator pair (1) or zero-extending moves and a 64-bit add (0).
-// Same-process A/B (tools/exp_variants.py) decides each default.
-#ifndef OFHE_QA_TCF
-#define OFHE_QA_TCF 0  // k_tcols forward
-#endif
-#ifndef OFHE_QA_TCI
-#define OFHE_QA_TCI 0  // k_tcols inverse
-#endif
-#ifndef OFHE_QA_BLK
-#define OFHE_QA_BLK 0  // k_block
-#endif
-#ifndef OFHE_QA_CF
-#define OFHE_QA_CF 0  // k_cols forward
-#endif
-#ifndef OFHE_QA_CI
-#define OFHE_QA_CI 0  // k_cols inverse
-#endif
-#ifndef OFHE_QA_BCC
-#define OFHE_QA_BCC 0  // k_bconv_cols
-#endif
-template <bool SPQ, bool QA = false>
-__device__ __forceinline__ Mod<SPQ, QA> load_mod(const TowerConst& tc) {
-    return Mod<SPQ, QA>{tc.q, 4 * tc.q, 8 * tc.q, tc.nq, tc.nq4, 0 - 8 * tc.q, tc.spq_sh, tc.one};
+// Every kernel takes the Shoup quotient form QA = false (Mod<SPQ, QA>,
+// arith.hpp): zero-extending moves and a 64-bit add.
+template <bool SPQ>
+__device__ __forceinline__ Mod<SPQ> load_mod(const TowerConst& tc) {
+    return Mod<SPQ>{tc.q, 4 * tc.q, 8 * tc.q, tc.nq, tc.nq4, 0 - 8 * tc.q, tc.spq_sh, tc.one};
 }
 
 // Device view of a plan. Twiddles are interleaved (w, w') pairs so one
@@ -115,126 +96,59 @@ struct Tw {
 };
 
 // Streaming (non-temporal) access for polynomial data, so that the data
-// streaming through L2 does not evict the twiddles every block re-reads
-// (OFHE_NT, A/B switch).
-#ifndef OFHE_NT
-#define OFHE_NT 1
-#endif
+// streaming through L2 does not evict the twiddles every block re-reads.
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u64 ld_s(const u64* p) { return OFHE_NT ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void st_s(u64* p, u64 v) {
-    if (OFHE_NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
+__device__ __forceinline__ u64 ld_s(const u64* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void st_s(u64* p, u64 v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ u64x2 ld2_s(const u64* p) {
-    const u64x2* q = reinterpret_cast<const u64x2*>(p);
-    return OFHE_NT ? __builtin_nontemporal_load(q) : *q;
+    return __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(p));
 }
-__device__ __forceinline__ void st2_s(u64* p, u64x2 v) {
-    u64x2* q = reinterpret_cast<u64x2*>(p);
-    if (OFHE_NT)
-        __builtin_nontemporal_store(v, q);
-    else
-        *q = v;
-}
-// OFHE_ABL_NOTW (ablation builds only, wrong results): twiddles from
-// registers instead of memory, to measure what the loads cost.
+__device__ __forceinline__ void st2_s(u64* p, u64x2 v) { __builtin_nontemporal_store(v, reinterpret_cast<u64x2*>(p)); }
 __device__ __forceinline__ Tw ldtw(const u64* base, u32 idx) {
-#ifdef OFHE_ABL_NOTW
-    const u64 f = (u64)(uintptr_t)base ^ idx;
-    return Tw{f & 0x0fffffffffffffffull, f * 0x9E3779B97F4A7C15ull};
-#else
     const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(base + 2 * (u64)idx);
     return Tw{v.x, v.y};
-#endif
 }
 
-// Cooley-Tukey butterfly.  Two lazy-reduction schemes (OFHE_LAZY_FWD):
-//  0: every stage subtracts 4q from x when x >= 4q; values stay in [0, 8q).
-//  1: stages alternate.  A "CS" stage (odd stage of a radix-16 round, the
-//     last stage of a column pass) subtracts 8q when x >= 8q and maps
-//     [0, 16q) -> [0, 12q); the other stages skip the conditional subtract and
-//     map [0, 12q) -> [0, 16q).  16q <= 2^64 because q < 2^60, and shoup_lazy
-//     accepts any 64-bit input, so half of the butterflies save the compare,
-//     two selects and the 64-bit subtract.
-#ifndef OFHE_LAZY_FWD
-#define OFHE_LAZY_FWD 1
-#endif
-// OFHE_THR (special primes q = 2^L - d only): the CS stages subtract 8q when
-// bit L+3 of x is set instead of comparing with 8q: one bit-field extract and
-// two ANDs build the mask, one 64-bit add applies it -- no compare, no VCC,
-// no selects.  2^(L+3) > 8q, so the invariant becomes [0, 2^(L+3) + 8q)
-// (< 2^(L+4) <= 2^64, where the bit test is exact); canon_fwd takes one more
-// conditional subtract.  Measured 3 % slower in the block pass despite the
-// shorter instruction stream (tools/exp_variants.py), so it is off.
-#ifndef OFHE_THR
-#define OFHE_THR 0
-#endif
-template <bool SPQ, bool QA>
-__device__ __forceinline__ u64 csub_thr8(u64 x, const Mod<SPQ, QA>& M) {
-    const u32 m = (u32)__builtin_amdgcn_sbfe((int)hi32(x), M.sh + 3, 1);
-    return x + pack(m & lo32(M.nq8), m & hi32(M.nq8));
-}
-// OFHE_FOLD (special primes): the lazy reductions [0, 16q) -> [0, 8q) (CS
-// stages, GS sums) use fold_spq (3 instructions, result < 2q) instead of the
-// conditional subtract (4).  OFHE_BFLY_ACC: the butterfly's x + w y is the
-// Shoup product with x as the addend of its first multiply-add, and
-// x - w y = (2x + 4q) - (x + w y): one 64-bit add fewer per butterfly.
-#ifndef OFHE_FOLD
-#define OFHE_FOLD 1
-#endif
-#ifndef OFHE_BFLY_ACC
-#define OFHE_BFLY_ACC 1
-#endif
-// [0, 16q) -> [0, 8q) ([0, 2q) by the fold)
+// Cooley-Tukey butterfly with alternating lazy reduction.  A "CS" stage (odd
+// stage of a radix-16 round, the last stage of a column pass) reduces x from
+// [0, 16q) to [0, 8q) first and maps [0, 16q) -> [0, 12q); the other stages
+// skip the reduction and map [0, 12q) -> [0, 16q).  16q <= 2^64 because
+// q < 2^60, and shoup_lazy accepts any 64-bit input, so half of the
+// butterflies save the compare, two selects and the 64-bit subtract.  The
+// output after a CS stage is < 12q, which mont_mul and the forward-subtract
+// of the block pass need.
+// [0, 16q) -> [0, 8q): a conditional subtract (4 instructions), or for the
+// special primes fold_spq (3 instructions, result < 2q)
 template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 red16(u64 x, const Mod<SPQ, QA>& M) {
-    if (SPQ && OFHE_FOLD) return fold_spq(x, M);
+    if (SPQ) return fold_spq(x, M);
     return csub_s(x, M.q8);
 }
-// The Gentleman-Sande sums keep the conditional subtract by default
-// (OFHE_FOLD_GS=0): same-process A/B, the inverse column pass was 1 % slower
-// with the fold there (profiles/r04a_fold_acc_ab.txt, r04b_qh2_ab.txt).
-#ifndef OFHE_FOLD_GS
-#define OFHE_FOLD_GS 0
-#endif
-// [0, 8q) -> [0, 4q) ([0, 2q) by the fold)
-template <bool SPQ, bool QA>
-__device__ __forceinline__ u64 red8(u64 x, const Mod<SPQ, QA>& M) {
-    if (SPQ && OFHE_FOLD && OFHE_FOLD_GS) return fold_spq(x, M);
-    return csub_s(x, M.q4);
-}
-// GS sums [0, 16q) -> [0, 8q)
-template <bool SPQ, bool QA>
-__device__ __forceinline__ u64 red16_gs(u64 x, const Mod<SPQ, QA>& M) {
-    if (SPQ && OFHE_FOLD && OFHE_FOLD_GS) return fold_spq(x, M);
-    return csub_s(x, M.q8);
-}
+// The butterfly's x + w y is the Shoup product with x as the addend of its
+// first multiply-add, and x - w y = (2x + 4q) - (x + w y): one 64-bit add
+// fewer per butterfly.
 template <bool SPQ, bool QA>
 __device__ __forceinline__ void ct_bfly_cs(u64& x, u64& y, Tw w, const Mod<SPQ, QA>& M, bool cs) {
-    u64 a;
-    if (OFHE_LAZY_FWD)
-        a = cs ? ((SPQ && OFHE_THR) ? csub_thr8(x, M) : red16(x, M)) : x;
-    else
-        a = csub_s(x, M.q4);
-    if (OFHE_BFLY_ACC == 2) {
-        const u64 c2 = (a << 1) + M.q4;          // computed first: a dies in the mad chain
-        x = shoup_lazy_acc(y, w.w, w.wp, M, a);  // a + [0, 4q)
-        y = c2 - x;                              // a + 4q - [0, 4q)
-    } else if (OFHE_BFLY_ACC) {
-        x = shoup_lazy_acc(y, w.w, w.wp, M, a);  // a + [0, 4q)
-        y = (a << 1) + M.q4 - x;                 // a + 4q - [0, 4q)
-    } else {
-        const u64 t = shoup_lazy(y, w.w, w.wp, M);  // [0, 4q)
-        x = a + t;
-        y = a + M.q4 - t;
-    }
+    const u64 a = cs ? red16(x, M) : x;
+    x = shoup_lazy_acc(y, w.w, w.wp, M, a);  // a + [0, 4q)
+    y = (a << 1) + M.q4 - x;                 // a + 4q - [0, 4q)
 }
 template <int CS, class M_>
 __device__ __forceinline__ void ct_bfly(u64& x, u64& y, Tw w, const M_& M) {
     ct_bfly_cs(x, y, w, M, CS != 0);
+}
+
+// The Gentleman-Sande sums take the conditional subtract for every modulus:
+// the fold made the inverse column pass slower.
+// [0, 8q) -> [0, 4q)
+template <bool SPQ, bool QA>
+__device__ __forceinline__ u64 red8(u64 x, const Mod<SPQ, QA>& M) {
+    return csub_s(x, M.q4);
+}
+// [0, 16q) -> [0, 8q)
+template <bool SPQ, bool QA>
+__device__ __forceinline__ u64 red16_gs(u64 x, const Mod<SPQ, QA>& M) {
+    return csub_s(x, M.q8);
 }
 
 // Gentleman-Sande butterfly, inputs in [0, 4q), outputs in [0, 4q).
@@ -259,9 +173,6 @@ __device__ __forceinline__ u64 canon4(u64 x, u64 q) {  // [0, 4q) -> [0, q)
 // x < 2^(L+4) -> [0, q) with one quotient by shift.  qh = x >> L < 16,
 // r = (x mod 2^L) + qh d = x - qh q < 2^L + 15 d = q + 16 d < 2q, one
 // conditional subtract: 3 + 4 instructions against 12 (canon8) or 16 (canon_fwd).
-#ifndef OFHE_SPQ_CANON
-#define OFHE_SPQ_CANON 1
-#endif
 template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 canon_spq(u64 x, const Mod<SPQ, QA>& M) {
     const u32 qh = hi32(x) >> M.sh;
@@ -271,19 +182,18 @@ __device__ __forceinline__ u64 canon_spq(u64 x, const Mod<SPQ, QA>& M) {
 }
 template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 canon8m(u64 x, const Mod<SPQ, QA>& M) {  // [0, 8q) -> [0, q)
-    return (SPQ && OFHE_SPQ_CANON) ? canon_spq(x, M) : canon8(x, M.q);
+    return SPQ ? canon_spq(x, M) : canon8(x, M.q);
 }
 template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 canon4m(u64 x, const Mod<SPQ, QA>& M) {  // [0, 4q) -> [0, q)
-    return (SPQ && OFHE_SPQ_CANON) ? canon_spq(x, M) : canon4(x, M.q);
+    return SPQ ? canon_spq(x, M) : canon4(x, M.q);
 }
 // forward-transform output (any stage pattern) -> [0, q)
 template <bool SPQ, bool QA>
 __device__ __forceinline__ u64 canon_fwd(u64 x, const Mod<SPQ, QA>& M) {
-    if (SPQ && OFHE_SPQ_CANON && !OFHE_THR) return canon_spq(x, M);  // < 16q < 2^(L+4)
+    if (SPQ) return canon_spq(x, M);  // < 16q < 2^(L+4)
     const u64 q = M.q;
-    if (SPQ && OFHE_THR) x = csub_s(x, 8 * q);  // [0, 2^(L+3) + 8q) -> [0, 8q + 8d)
-    if (OFHE_LAZY_FWD) x = csub_s(x, 8 * q);    // [0, 16q) -> [0, 8q)
+    x = csub_s(x, 8 * q);  // [0, 16q) -> [0, 8q)
     return canon8(x, q);
 }
 
@@ -310,7 +220,6 @@ __device__ __forceinline__ u64 canon_fwd(u64 x, const Mod<SPQ, QA>& M) {
 // moves here from GS's first stage; for G = N it is N^-1 psi^-j).  Same
 // canonical outputs, bit for bit.
 // ---------------------------------------------------------------------------
-static_assert(OFHE_LAZY_FWD, "the DIT inverse uses the alternating lazy CT butterflies");
 
 // x + y and x + B q - y for y < B q (B q passed as bq): the w = 1 butterfly
 __device__ __forceinline__ void triv_bfly(u64& x, u64& y, u64 bq) {
@@ -411,15 +320,12 @@ __device__ __forceinline__ void inv_stage16(u64 (&v)[16], const u64* itw, u32 M0
     }
 }
 
-// Lazy GS radix-16 round for the inverse column pass (OFHE_LAZY_GS).  The
+// Lazy GS radix-16 round for the inverse column pass.  The
 // bound of every register is known at compile time (b8[k]: < 8q, else < 4q):
 // a GS butterfly's sum output is < 8q and its Shoup output < 4q whatever the
 // inputs, so only butterflies with an 8q input take the conditional subtract
 // (12 of 32 in a round fed with < 4q, 20 of 32 fed with < 8q) and the rest
 // add straight through.  d = x + Bq - y < 16q <= 2^64 (q < 2^60).
-#ifndef OFHE_LAZY_GS
-#define OFHE_LAZY_GS 1
-#endif
 template <class M_>
 __device__ __forceinline__ void gs_bfly_b(u64& x, u64& y, Tw w, const M_& M, bool in8) {
     const u64 s = x + y;
@@ -457,17 +363,14 @@ __device__ __forceinline__ void fwd_round16(u64 (&v)[16], const u64* tw, u32 M0,
     fwd_stage16<2>(v, tw, M0, M);
     fwd_stage16<3>(v, tw, M0, M);
 }
-// First round of a forward transform on canonical input (OFHE_FWD_CANON):
+// First round of a forward transform on canonical input:
 // [0, q) -> 5q -> 9q -> 13q without a conditional subtract, then the CS stage
 // -> [0, 12q), the bound the alternating schedule leaves after any round.
 // Needs inputs < 4q (canonical, per the C ABI contract).
-#ifndef OFHE_FWD_CANON
-#define OFHE_FWD_CANON 1
-#endif
 template <class M_>
 __device__ __forceinline__ void fwd_round16_canon(u64 (&v)[16], const u64* tw, u32 M0, const M_& M) {
     fwd_stage16<0>(v, tw, M0, M);
-    fwd_stage16<1, M_, OFHE_FWD_CANON ? 0 : 1>(v, tw, M0, M);
+    fwd_stage16<1, M_, 0>(v, tw, M0, M);
     fwd_stage16<2>(v, tw, M0, M);
     fwd_stage16<3>(v, tw, M0, M);
 }
@@ -487,31 +390,19 @@ __device__ __forceinline__ void inv_round16(u64 (&v)[16], const u64* itw, u32 M0
 // plan therefore also stores these twiddles transposed, tw3[S][j][u] at
 // ((2^S - 1) U + j U + u) with U = N/16, so a wave reads 1 KiB contiguous per
 // load, from a uniform (scalar) base plus the lane offset.
-// ---------------------------------------------------------------------------
-#ifndef OFHE_TW3
-#define OFHE_TW3 1
-#endif
-// OFHE_MONT: the fused pipeline's Hadamard is a Montgomery product on the lazy
-// forward output (no canonicalisation, no Barrett), and the 2^-64 it
-// introduces is cancelled by 2^64 folded into the inverse's N^-1 twist
-// (PlanArgs::twist = the plan's twist_r table).  Intermediate values differ in representation only;
-// the canonical output is the same integer.
-#ifndef OFHE_MONT
-#define OFHE_MONT 1
-#endif
+//
+// The fused pipeline's Hadamard is a Montgomery product on the lazy forward
+// output (< 12q after round 3's CS stage, which mont_mul accepts; no
+// canonicalisation, no Barrett), and the 2^-64 it introduces is cancelled by
+// 2^64 folded into the inverse's N^-1 twist (PlanArgs::twist = the plan's
+// twist_r table).  Intermediate values differ in representation only; the
+// canonical output is the same integer.
+//
 // k_block's round-3 layout gives each thread 16 consecutive words, so direct
-// global access is one 128-byte line per lane per instruction.  With
-// OFHE_COAL (inverse input, forward output) and OFHE_COAL_B (the Hadamard
-// operand) these go through the wave's own LDS slots instead (wave_stage_*).
-#ifndef OFHE_COAL
-#define OFHE_COAL 1
-#endif
-#ifndef OFHE_COAL_B
-#define OFHE_COAL_B 1
-#endif
-constexpr bool kMontFused = OFHE_MONT && OFHE_COAL_B;
-// mont_mul takes a < 12q: the forward output after a CS stage (OFHE_THR widens it)
-static_assert(!(kMontFused && OFHE_THR), "Montgomery Hadamard needs the forward output < 12q");
+// global access would be one 128-byte line per lane per instruction.  The
+// inverse input, the forward output and the second operand go through the
+// wave's own LDS slots instead (wave_stage_*).
+// ---------------------------------------------------------------------------
 template <int S, class M_>
 __device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[16], const u64* tw3, u32 U, u32 u, const M_& M) {
     constexpr int half = 8 >> S;
@@ -680,10 +571,9 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
     const u32 wq = TEAM ? 0 : (tid >> 6) * 1024;
     const u64* blk = src + (u64)b * P.sstride + inner;
     u64* oblk = dst + off;
-    const u32 e3 = (TEAM ? r : tid) * 16;  // the thread's 16 round-3 words, from blk / oblk
     const TowerConst tc = P.tc[t];
     const u64 q = tc.q;
-    const auto M = load_mod<SPQ, (bool)OFHE_QA_BLK>(tc);
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
     const u64* tw = P.tw + (u64)t * N * 2;
     // padded LDS bases (lds_pad(p) = p + p/16) of the three round layouts
     const u32 L1 = tid + h;      // lds_pad(tid + 256 k)      = L1 + 272 k
@@ -722,28 +612,25 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
         // the first OFHE_B_PF of its 8 wave-coalesced 16-byte loads go out
         // now, so their HBM latency hides under round 3 (same-process A/B,
         // batch 256: fused block pass 1.740 -> 1.673 ms, VGPRs unchanged)
-        constexpr int BPF = ((MODE == MODE_FUSED && OFHE_COAL_B) || MODE == MODE_FWD_SUB) ? OFHE_B_PF : 0;
+        constexpr int BPF = (MODE == MODE_FUSED || MODE == MODE_FWD_SUB) ? OFHE_B_PF : 0;
         u64x2 bpre[BPF > 0 ? BPF : 1];
 #pragma unroll
         for (int k = 0; k < BPF; k++) bpre[k] = ld2_s(bdat + boff + wq + StageMap<TEAM>(tid).g(k));
-        if (OFHE_TW3) {
+        {
             const u64* tw3 = P.tw3 + (u64)t * (N / 16) * 30;
             const u32 U = N >> 4, u = TEAM ? g * 16 + r : g * 256 + tid;
             fwd_stage16_t3<0>(v, tw3, U, u, M);
             fwd_stage16_t3<1>(v, tw3, U, u, M);
             fwd_stage16_t3<2>(v, tw3, U, u, M);
             fwd_stage16_t3<3>(v, tw3, U, u, M);
-        } else {
-            fwd_round16(v, tw, (N >> 4) + (TEAM ? g * 16 + r : g * 256 + tid), M);
         }
-        if (!(MODE == MODE_FUSED && kMontFused) && MODE != MODE_FWD_SUB) {
+        if (MODE == MODE_FWD) {
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = canon_fwd<SPQ>(v[k], M);
+            wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
+            return;
         }
         if (MODE == MODE_FWD_SUB) {
-            // x + 12q - v needs the forward output v < 12q; OFHE_THR's bit-test
-            // reduction leaves it below 2^(L+3) + 8q (up to 16q), which could wrap
-            static_assert(!OFHE_THR, "the lazy forward-subtract needs the forward output < 12q (OFHE_THR widens it)");
             // (x - NTT(y)) s mod q without canonicalising NTT(y) first: v < 12q
             // (round 3 ends with a CS stage), so d = x + 12q - v is in (0, 13q)
             // < 2^64, the lazy Shoup takes any 64-bit input to [0, 4q), and one
@@ -758,53 +645,15 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
             return;
         }
-        if (MODE == MODE_FWD) {
-            if (OFHE_COAL) {
-                wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
-            } else {
-                ulonglong2* o = reinterpret_cast<ulonglong2*>(oblk + e3);
+        // Hadamard with b (evaluation form), NativeVectorT::ModMulNoCheckEq, as
+        // a Montgomery product on the lazy forward output (< 12q)
+        u64 bb[16];
+        wave_stage_in_pre<TEAM, BPF>(bdat + boff + wq, lds, tid, bpre, bb);
 #pragma unroll
-                for (int k = 0; k < 8 && live; k++) o[k] = make_ulonglong2(v[2 * k], v[2 * k + 1]);
-            }
-            return;
-        }
-        // Hadamard with b (evaluation form), NativeVectorT::ModMulNoCheckEq
-        if (OFHE_COAL_B) {
-            u64 bb[16];
-            wave_stage_in_pre<TEAM, BPF>(bdat + boff + wq, lds, tid, bpre, bb);
-            if (kMontFused) {
-#pragma unroll
-                for (int k = 0; k < 16; k++) v[k] = mont_mul(v[k], bb[k], q, tc.qinv);  // (0, 2q)
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; k++) v[k] = barrett_ref(v[k], bb[k], q, tc.mu, tc.nshift);
-            }
-        } else {
-            const ulonglong2* bp = reinterpret_cast<const ulonglong2*>(bdat + boff + e3);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-#ifdef OFHE_ABL_NOB
-                ulonglong2 bb = make_ulonglong2(v[k] ^ off, v[k + 8] ^ tid);
-#else
-                ulonglong2 bb = bp[k];
-#endif
-                v[2 * k] = barrett_ref(v[2 * k], bb.x, q, tc.mu, tc.nshift);
-                v[2 * k + 1] = barrett_ref(v[2 * k + 1], bb.y, q, tc.mu, tc.nshift);
-            }
-        }
+        for (int k = 0; k < 16; k++) v[k] = mont_mul(v[k], bb[k], q, tc.qinv);  // (0, 2q)
         // no barrier: round 3' below rewrites only this thread's own LDS slots
     } else {
-        if (OFHE_COAL) {
-            wave_stage_in<TEAM>(blk + wq, lds, tid, v);
-        } else {
-            const ulonglong2* ip = reinterpret_cast<const ulonglong2*>(blk + e3);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                ulonglong2 a = ip[k];
-                v[2 * k] = a.x;
-                v[2 * k + 1] = a.y;
-            }
-        }
+        wave_stage_in<TEAM>(blk + wq, lds, tid, v);
     }
     // inverse as DIT inside the block's groups: round 3' (t = 1..8, uniform
     // twiddles), round 2' (t = 16..128, st = 16, r = tid & 15), round 1'
@@ -886,23 +735,11 @@ struct SwSrc {
 #define OFHE_TCOLS_W 16  // tile width in columns: 16 (128-byte row segments) or 32 (256-byte)
 #endif
 constexpr u32 TCOLS_W = OFHE_TCOLS_W;
-#ifndef OFHE_TCOLS_PADF
-#define OFHE_TCOLS_PADF 1
-#endif
 static_assert(TCOLS_W == 16 || TCOLS_W == 32, "column tile width");
 // LOGN = 17 (the 8 | 9 split, SPLIT_T8B9): element j = row * 512 + col, the
 // same 256-row sub-transforms on 512 columns (the twiddle index of stage m is
 // m + row / (256 / m) whatever the row length).
 constexpr u32 TCOLS_LDS_WORDS = 16 * 16 * TCOLS_W + 16 * 16;
-// OFHE_TCOLS_HALF: the inverse column pass transposes through half the LDS in
-// two passes (A/B knob), its kernel sized for OFHE_TCOLS_HALF_WAVES waves per SIMD
-#ifndef OFHE_TCOLS_HALF
-#define OFHE_TCOLS_HALF 0
-#endif
-#ifndef OFHE_TCOLS_HALF_WAVES
-#define OFHE_TCOLS_HALF_WAVES 5
-#endif
-constexpr u32 TCOLS_LDS_INV_WORDS = OFHE_TCOLS_HALF ? 8 * 16 * TCOLS_W : TCOLS_LDS_WORDS;
 // The body of k_tcols for work item wid (column tile cb = wid % (S / W) of
 // polynomial tower pb = wid / (S / W)) on the caller's LDS (TCOLS_LDS_WORDS).
 template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16>
@@ -915,9 +752,9 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
     // both conflict free (SQ_LDS_BANK_CONFLICT = 0; a p + p/16 padding made its
     // 32-lane ds_read_b64 groups 2-way conflicted).  The forward READS the
     // second pattern, where a half-wave's two rows h, h + 1 hit the same 32
-    // banks (2-way, measured 0.56 conflict cycles per active LDS cycle); with
-    // OFHE_TCOLS_PADF it shifts row h by 16 words per 16W-word row
-    // (lds index p + 16 (p / 16W)), so rows h and h + 1 cover all 64 banks.
+    // banks (2-way, measured 0.56 conflict cycles per active LDS cycle); so it
+    // shifts row h by 16 words per 16W-word row (lds index p + 16 (p / 16W),
+    // the row pitch RP), and rows h and h + 1 cover all 64 banks.
     const u32 cb = wid % (S / W);
     const u32 pb = wid / (S / W);
     const u32 t = pb / batch, b = pb % batch;
@@ -925,13 +762,13 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
     const u64* x = src + (u64)b * P.sstride + inner;
     u64* y = dst + (u64)b * P.dstride + inner;
     const TowerConst tc = P.tc[t];
-    const auto M = load_mod<SPQ, INV ? (bool)OFHE_QA_TCI : (bool)OFHE_QA_TCF>(tc);
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
     const u32 h = tid / W, r = tid % W;
     const u32 L1 = tid, L2 = h * 16 * W + r;
     u64 v[16];
     if (!INV) {
         const u64* tw = P.tw + (u64)t * N * 2;
-        constexpr u32 RP = OFHE_TCOLS_PADF ? 16 * W + 16 : 16 * W;  // padded row pitch
+        constexpr u32 RP = 16 * W + 16;  // padded row pitch
         // round 1: rows h + 16k (p = tid + 16W k), stages m = 1..8
         if (SWS) {
             const u64 w = SWA.tab[6 * t + 1], wp = SWA.tab[6 * t + 2];
@@ -962,72 +799,32 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
         const u64* itw = P.itw + (u64)t * N * 2;
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = ld_s(x + (u64)(16 * h + k) * S + r);
-        if (OFHE_LAZY_GS) {
-            // input < 4q (the block pass's lazy twist); round 2's registers all
-            // come from one round-1 position, taken as < 8q
-            bool b8[16];
+        // input < 4q (the block pass's lazy twist); round 2's registers all
+        // come from one round-1 position, taken as < 8q
+        bool b8[16];
 #pragma unroll
-            for (int k = 0; k < 16; k++) b8[k] = false;
-            inv_round16_b(v, b8, itw, 16 + h, M);
-            if (OFHE_TCOLS_HALF) {
-                // the transpose through half the LDS (8 W x 16 words) in two
-                // passes: writers h < 8, then h >= 8 (wave-uniform), every
-                // thread reading 8 values per pass; 16 KiB per workgroup lets
-                // more workgroups share a CU (A/B knob)
-                u64 o[16];
-                if (h < 8) {
+        for (int k = 0; k < 16; k++) b8[k] = false;
+        inv_round16_b(v, b8, itw, 16 + h, M);
 #pragma unroll
-                    for (int k = 0; k < 16; k++) lds[L2 + W * k] = v[k];
-                }
-                __syncthreads();
+        for (int k = 0; k < 16; k++) lds[L2 + W * k] = v[k];
+        __syncthreads();
 #pragma unroll
-                for (int k = 0; k < 8; k++) o[k] = lds[L1 + 16 * W * k];
-                __syncthreads();
-                if (h >= 8) {
-#pragma unroll
-                    for (int k = 0; k < 16; k++) lds[L2 - 8 * 16 * W + W * k] = v[k];
-                }
-                __syncthreads();
-#pragma unroll
-                for (int k = 8; k < 16; k++) o[k] = lds[L1 + 16 * W * (k - 8)];
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    v[k] = o[k];
-                    b8[k] = true;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 16; k++) lds[L2 + W * k] = v[k];
-                __syncthreads();
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    v[k] = lds[L1 + 16 * W * k];
-                    b8[k] = true;
-                }
-            }
-            inv_round16_b(v, b8, itw, 1, M);
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                st_s(y + (u64)(h + 16 * k) * S + r, b8[k] ? canon8m(v[k], M) : canon4m(v[k], M));
-        } else {
-            inv_round16(v, itw, 16 + h, M);
-#pragma unroll
-            for (int k = 0; k < 16; k++) lds[L2 + W * k] = v[k];
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = lds[L1 + 16 * W * k];
-            inv_round16(v, itw, 1, M);
-#pragma unroll
-            for (int k = 0; k < 16; k++) st_s(y + (u64)(h + 16 * k) * S + r, canon4m(v[k], M));
+        for (int k = 0; k < 16; k++) {
+            v[k] = lds[L1 + 16 * W * k];
+            b8[k] = true;
         }
+        inv_round16_b(v, b8, itw, 1, M);
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            st_s(y + (u64)(h + 16 * k) * S + r, b8[k] ? canon8m(v[k], M) : canon4m(v[k], M));
     }
 }
 
 template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16>
-__global__ __launch_bounds__(16 * TCOLS_W, (INV && OFHE_TCOLS_HALF) ? OFHE_TCOLS_HALF_WAVES : OFHE_KB_WAVES) void k_tcols(
-    PlanArgs P, const u64* src, u64* dst, u32 batch, u32 nwg, SwSrc SWA) {
+__global__ __launch_bounds__(16 * TCOLS_W, OFHE_KB_WAVES) void k_tcols(PlanArgs P, const u64* src, u64* dst, u32 batch,
+                                                                       u32 nwg, SwSrc SWA) {
     OFHE_VGPR_FLOOR();
-    __shared__ u64 lds[INV ? TCOLS_LDS_INV_WORDS : TCOLS_LDS_WORDS];
+    __shared__ u64 lds[TCOLS_LDS_WORDS];
     tcols_body<INV, SPQ, SWS, LOGN>(P, src, dst, batch, xcd_remap(blockIdx.x, nwg), SWA, lds, threadIdx.x);
 }
 
@@ -1148,23 +945,7 @@ __device__ __forceinline__ void cols_fwd(u64 (&v)[CPT][E], const u64* tw, const 
         }
     }
 }
-template <int E, int CPT, class M_>
-__device__ __forceinline__ void cols_inv(u64 (&v)[CPT][E], const u64* itw, const M_& M) {
-    constexpr int KA = __builtin_ctz(E);
-#pragma unroll
-    for (int s = KA - 1; s >= 0; s--) {
-        const int half = E >> (s + 1);
-#pragma unroll
-        for (int j = 0; j < (1 << s); j++) {
-            Tw w = ldtw(itw, (1u << s) + j);
-#pragma unroll
-            for (int k = j * 2 * half; k < j * 2 * half + half; k++)
-#pragma unroll
-                for (int c = 0; c < CPT; c++) gs_bfly(v[c][k], v[c][k + half], w, M);
-        }
-    }
-}
-// lazy form (OFHE_LAZY_GS): compile-time bounds b8 as in inv_stage16_b, inputs < 4q
+// lazy GS: compile-time bounds b8 as in inv_stage16_b, inputs < 4q
 template <int E, int CPT, class M_>
 __device__ __forceinline__ void cols_inv_b(u64 (&v)[CPT][E], bool (&b8)[E], const u64* itw, const M_& M) {
     constexpr int KA = __builtin_ctz(E);
@@ -1202,7 +983,7 @@ __global__ __launch_bounds__(256) void k_cols(PlanArgs P, const u64* src, u64* d
     const u64* x = src + (u64)b * P.sstride + inner;
     u64* y = dst + (u64)b * P.dstride + inner;
     const TowerConst tc = P.tc[t];
-    const auto M = load_mod<SPQ, INV ? (bool)OFHE_QA_CI : (bool)OFHE_QA_CF>(tc);
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
     u64 v[CPT][E];
     if (SWS) {
         const u64 w = S.tab[6 * t + 1], wp = S.tab[6 * t + 2];
@@ -1241,20 +1022,12 @@ __global__ __launch_bounds__(256) void k_cols(PlanArgs P, const u64* src, u64* d
     if (!INV) {
         cols_fwd<E, CPT>(v, P.tw + (u64)t * N * 2, M);
     } else {
-        if (OFHE_LAZY_GS) {
-            bool b8[E];
-            cols_inv_b<E, CPT>(v, b8, P.itw + (u64)t * N * 2, M);
+        bool b8[E];
+        cols_inv_b<E, CPT>(v, b8, P.itw + (u64)t * N * 2, M);
 #pragma unroll
-            for (int k = 0; k < E; k++)
+        for (int k = 0; k < E; k++)
 #pragma unroll
-                for (int c = 0; c < CPT; c++) v[c][k] = b8[k] ? canon8m(v[c][k], M) : canon4m(v[c][k], M);
-        } else {
-            cols_inv<E, CPT>(v, P.itw + (u64)t * N * 2, M);
-#pragma unroll
-            for (int k = 0; k < E; k++)
-#pragma unroll
-                for (int c = 0; c < CPT; c++) v[c][k] = canon4m(v[c][k], M);
-        }
+            for (int c = 0; c < CPT; c++) v[c][k] = b8[k] ? canon8m(v[c][k], M) : canon4m(v[c][k], M);
     }
 #pragma unroll
     for (int k = 0; k < E; k++) {

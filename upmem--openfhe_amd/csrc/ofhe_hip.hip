@@ -523,11 +523,11 @@ static PlanArgs args_of(ofhe_plan_t p, u32 t0 = 0, u32 count = 0) {
     return a;
 }
 
-// Fused pipeline: with the Montgomery Hadamard (kMontFused, log_n >= 12) the
+// Fused pipeline: with the block pass's Montgomery Hadamard (log_n >= 12) the
 // inverse output twist also carries 2^64 to cancel its 2^-64.
 static PlanArgs fused_args(ofhe_plan_t p) {
     PlanArgs a = args_of(p);
-    if (kMontFused && p->log_n >= 12) a.twist = p->d_twist_r;
+    if (p->log_n >= 12) a.twist = p->d_twist_r;
     return a;
 }
 
@@ -962,7 +962,7 @@ static bool bconv_mma_table(u32 size_q, u32 size_p, const u64* q, const u64* p, 
             }
     BmRed* red = reinterpret_cast<BmRed*>(tab.data() + fbytes);
     // special-prime reduction (bm_reduce<.., SPQ>) when every target allows it
-    spq = OFHE_BCONV_MMA_SPQ != 0;
+    spq = true;
     for (u32 j = 0; j < size_p && spq; j++) {
         const unsigned L = msb64(p[j]);
         const u64 d = L >= 33 && L <= 60 ? (1ull << L) - p[j] : 0;
@@ -1099,7 +1099,7 @@ namespace ofhe {
 // WIDE) runs that kernel on every path, the fused ModUp / ModDown column
 // kernel included: only OFHE_BCONV_KERNEL_AUTO may take k_bconv_cols.
 bool bconv_cols_ok(ofhe_plan_t p, const BconvArgs& B) {
-    return OFHE_BCONV_MMA && B.kernel == OFHE_BCONV_KERNEL_AUTO && p && p->log_n == 17 && B.log_n == 17 && p->split == SPLIT_COLS && B.mm_tab &&
+    return B.kernel == OFHE_BCONV_KERNEL_AUTO && p && p->log_n == 17 && B.log_n == 17 && p->split == SPLIT_COLS && B.mm_tab &&
            B.mm_ks >= 1 && B.mm_ks <= 4 && (B.mm_spq != 0) == p->spq;
 }
 
@@ -1126,8 +1126,7 @@ int bconv_cols_run(ofhe_plan_t p, u32 t0, const BconvArgs& B, const u64* x, u64*
 // converter: the matrix cores for <= 64 sources and N >= 32 unless the handle
 // asks for LIMB / WIDE, over the instantiated K-step counts.
 static bool bconv_use_mma(const BconvArgs& A) {
-    return OFHE_BCONV_MMA && A.mm_tab && A.log_n >= 5 && A.kernel != OFHE_BCONV_KERNEL_WIDE &&
-           A.kernel != OFHE_BCONV_KERNEL_LIMB;
+    return A.mm_tab && A.log_n >= 5 && A.kernel != OFHE_BCONV_KERNEL_WIDE && A.kernel != OFHE_BCONV_KERNEL_LIMB;
 }
 struct MmaShape {
     dim3 grid;
