@@ -10,9 +10,20 @@ at function symbols, and every kernel's text -- instructions, its .amdhsa_kernel
 descriptor, and its entry of the amdhsa.kernels metadata (registers, LDS,
 scratch, argument layout) -- is compared by mangled name.  Local labels carry
 the function's ordinal in the file, which a deleted kernel shifts, so the
-ordinal is dropped; so are the __hip_cuid_ lines, a hash of the source text.
+ordinal is dropped (in labels and in the loop comments that cite them, with
+the padding that aligns a label's comment); so are the __hip_cuid_ lines, a
+hash of the source text, and the .section line that closes a function's text
+by naming the next function.
 What lies outside any function is compared as "(file scope)".  Exit status 1
 when a kernel differs or exists only in the second tree.
+
+A template that gained a defaulted parameter keeps its code and changes its
+mangled name; `--rename REGEX REPL` (repeatable) rewrites the first tree's
+assembly with re.sub before it is cut, so that such kernels are compared
+under their new names:
+
+    python tools/isa_diff.py PARENT_CSRC upmem--openfhe_amd/csrc \\
+        --rename '(k_blockILi\\d+ELb[01]ELi\\d+ELi\\d+E)EE' '\\1Li1EEE'
 """
 import os
 import re
@@ -25,7 +36,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 MAKEFILE = os.path.join(HERE, "..", "upmem--openfhe_amd", "csrc", "Makefile")
 BEGIN = re.compile(r"; -- Begin function (\S+)")  # on the symbol's .globl or .weak line
 OBJECT = re.compile(r"^\s*\.type\s+\S+,@object")
-ORDINAL =re.compile(r"(\.L(?:BB|func_(?:begin|end)|JTI|tmp|CPI))\d+")
+NEXT_SECTION = re.compile(r"^\s*\.section\s+\.text\.")  # ends a function's text and names the next function
+PAD = re.compile(r"\s+;")  # a label's comment is aligned by the label's length, ordinal included
+ORDINAL = re.compile(r"(\.L(?:BB|func_(?:begin|end)|JTI|tmp|CPI)|\bBB(?=\d+_\d))\d+")  # BBn_m: loop comments
 
 
 def make_var(name, default=None):
@@ -47,7 +60,7 @@ def kernels(text):
     text, _, meta = text.partition("amdhsa.kernels:\n")
     parts, name = {"(file scope)": []}, "(file scope)"
     for line in text.splitlines():
-        if "__hip_cuid_" in line:
+        if "__hip_cuid_" in line or NEXT_SECTION.match(line):
             continue
         m = BEGIN.search(line)
         if m:
@@ -55,7 +68,7 @@ def kernels(text):
             parts[name] = []
         elif OBJECT.match(line):  # data objects follow the functions
             name = "(file scope)"
-        parts[name].append(ORDINAL.sub(r"\1", line))
+        parts[name].append(PAD.sub(" ;", ORDINAL.sub(r"\1", line)))
     for entry in re.split(r"^  - ", meta, flags=re.M)[1:]:
         m = re.search(r"^\s*\.name:\s*(\S+)", entry, re.M)
         if m:
@@ -63,10 +76,13 @@ def kernels(text):
     return {k: "\n".join(v) for k, v in parts.items()}
 
 
-def main(a, b):
+def main(a, b, renames=()):
     srcs = make_var("SRCS").split()
     with ThreadPoolExecutor(os.cpu_count() or 1) as pool:
         texts = list(pool.map(lambda job: assembly(*job), [(d, s) for s in srcs for d in (a, b)]))
+    for pattern, repl in renames:
+        print(f"first tree renamed: {pattern} -> {repl}")
+        texts[0::2] = [re.sub(pattern, repl, t) for t in texts[0::2]]
     bad = 0
     for i, src in enumerate(srcs):
         ka, kb = kernels(texts[2 * i]), kernels(texts[2 * i + 1])
@@ -83,4 +99,9 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])))
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append((args[i + 1], args[i + 2]))
+        del args[i:i + 3]
+    sys.exit(main(os.path.abspath(args[0]), os.path.abspath(args[1]), renames))

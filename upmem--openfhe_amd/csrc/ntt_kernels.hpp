@@ -414,6 +414,107 @@ __device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[16], const u64* tw3, u32
         for (int k = j * 2 * half; k < j * 2 * half + half; k++) ct_bfly<S & 1>(v[k], v[k + half], w, M);
     }
 }
+// ---------------------------------------------------------------------------
+// The same stages on Q register sets per thread (block_body_q2's two
+// polynomial quads): every twiddle or twist entry is fetched once and applied
+// to all sets before the next fetch, as cols_fwd's columns.  Per set, the
+// operations and their order are those of the one-set helpers above.
+// ---------------------------------------------------------------------------
+template <int S, int Q, class M_>
+__device__ __forceinline__ void fwd_stage16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = tw + 2 * ((u64)M0 << S);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base, j);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<S & 1>(v[c][k], v[c][k + half], w, M);
+    }
+}
+template <int Q, class M_>
+__device__ __forceinline__ void fwd_round16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    fwd_stage16<0>(v, tw, M0, M);
+    fwd_stage16<1>(v, tw, M0, M);
+    fwd_stage16<2>(v, tw, M0, M);
+    fwd_stage16<3>(v, tw, M0, M);
+}
+template <int S, int Q, class M_>
+__device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[Q][16], const u64* tw3, u32 U, u32 u, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = tw3 + 2 * (u64)(((1u << S) - 1) * U);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base + 2 * (u64)j * U, u);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<S & 1>(v[c][k], v[c][k + half], w, M);
+    }
+}
+template <int H, int CS, int Q, class M_>
+__device__ __forceinline__ void dit_stage16(u64 (&v)[Q][16], const u64* base, u32 st, const M_& M) {
+    constexpr int half = 1 << H;
+#pragma unroll
+    for (int j = 0; j < half; j++) {
+        const Tw w = ldtw(base, st * j);
+#pragma unroll
+        for (int g = 0; g < 16; g += 2 * half)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<CS>(v[c][g + j], v[c][g + j + half], w, M);
+    }
+}
+template <int Q, class M_>
+__device__ __forceinline__ void dit_round16(u64 (&v)[Q][16], const u64* dtw, u32 st, u32 r, const M_& M) {
+    dit_stage16<0, 1>(v, dtw + 2 * ((u64)st + r), st, M);
+    dit_stage16<1, 0>(v, dtw + 2 * ((u64)2 * st + r), st, M);
+    dit_stage16<2, 1>(v, dtw + 2 * ((u64)4 * st + r), st, M);
+    dit_stage16<3, 0>(v, dtw + 2 * ((u64)8 * st + r), st, M);
+}
+template <int Q, bool SPQ, bool QA>
+__device__ __forceinline__ void dit_round3(u64 (&v)[Q][16], const u64* dtw, const Mod<SPQ, QA>& M) {
+#pragma unroll
+    for (int c = 0; c < Q; c++) {
+#pragma unroll
+        for (int g = 0; g < 16; g += 2) triv_bfly(v[c][g], v[c][g + 1], 2 * M.q);
+#pragma unroll
+        for (int g = 0; g < 16; g += 4) triv_bfly(v[c][g], v[c][g + 2], M.q4);
+    }
+    {
+        const Tw w = ldtw(dtw, 3);
+#pragma unroll
+        for (int g = 0; g < 16; g += 4)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<0>(v[c][g + 1], v[c][g + 3], w, M);
+    }
+#pragma unroll
+    for (int c = 0; c < Q; c++)
+#pragma unroll
+        for (int g = 0; g < 16; g += 8) triv_bfly(v[c][g], v[c][g + 4], M.q8);
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        const Tw w = ldtw(dtw, 4 + j);
+#pragma unroll
+        for (int g = 0; g < 16; g += 8)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<0>(v[c][g + j], v[c][g + j + 4], w, M);
+    }
+#pragma unroll
+    for (int c = 0; c < Q; c++) {
+        const u64 a = red16(v[c][0], M), b = red16(v[c][8], M);
+        v[c][0] = a;
+        v[c][8] = b;
+        triv_bfly(v[c][0], v[c][8], M.q8);
+    }
+#pragma unroll
+    for (int j = 1; j < 8; j++) {
+        const Tw w = ldtw(dtw, 8 + j);
+#pragma unroll
+        for (int c = 0; c < Q; c++) ct_bfly<1>(v[c][j], v[c][j + 8], w, M);
+    }
+}
+
 // LDS placement of block element p: one u64 of padding per 16 elements.  It is
 // additive, so every round addresses its 16 values as one base register plus
 // immediate offsets, and it is bank-conflict free for the round-2/3 patterns
@@ -700,12 +801,145 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
 #pragma unroll
     for (int k = 0; k < 16; k++) st_s(oblk + tid + 256 * k, v[k]);
 }
-template <int MODE, bool SPQ, int NR, int SK = 0>
-__global__ __launch_bounds__(256, OFHE_KB_WAVES) void k_block(PlanArgs P, const u64* src, u64* dst,
-                                                              const u64* __restrict__ bdat, u32 batch, u32 nwg) {
+// The fused pipeline's NR = 2 block pass with two polynomial quads per thread
+// (k_block QP = 2, N = 2^16): set s of team tm is polynomial b = 8 bo + 4 s + tm
+// of the octet bo (octet-tower wid / G4 = t * ceil(batch / 8) + bo: half as
+// many items as block_body's quads), the group mapping g = 4 (wid % G4) + wave
+// is block_body's.  Every tw3 / DIT / twist line and every scalar twiddle a
+// wave fetches now serves eight polynomials: each helper applies an entry to
+// both sets before it fetches the next.  The sets go through the wave's LDS
+// slots one after the other (set 0 writes, wave_barrier, set 0 reads,
+// wave_barrier, set 1 writes, ...; LDS_WORDS as before): LDS runs one wave's
+// operations in the order they were issued, so set 1's writes cannot pass
+// set 0's reads once the compiler keeps that order, and the wave_barrier
+// between them is the fence that makes it keep it.  A batch tail can leave
+// teams of either set empty, set 1 as a whole when batch mod 8 is in 1..4:
+// they run clamped to the batch's last polynomial and store nothing, as
+// block_body's.  Same values in the same order of operations per polynomial
+// as block_body<MODE_FUSED, SPQ, 2>.
+template <bool SPQ>
+__device__ __forceinline__ void block_body_q2(const PlanArgs& P, const u64* src, u64* dst,
+                                              const u64* __restrict__ bdat, u32 batch, u32 wid, u64* lds, u32 tid) {
+    constexpr int QP = 2;
+    const u32 N = 1u << P.log_n;
+    const u32 h = tid >> 4, r = tid & 15;
+    const u32 G4 = N >> 10, no = (batch + 7) >> 3;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 g = (wid % G4) * 4 + wave;  // 256-element group, wave-uniform
+    const u32 po = wid / G4;
+    const u32 t = po / no;
+    const u64 inner = (u64)t * N + ((u64)g << 8);
+    bool live[QP];  // false: an empty team of the batch tail
+    u64 boff[QP];
+    const u64* blk[QP];
+    u64* oblk[QP];
+#pragma unroll
+    for (int s = 0; s < QP; s++) {
+        const u32 bt = (po % no) * 8 + 4 * s + (h & 3);
+        live[s] = bt < batch;
+        const u32 b = live[s] ? bt : batch - 1;
+        boff[s] = (u64)b * P.bstride + inner;
+        blk[s] = src + (u64)b * P.sstride + inner;
+        oblk[s] = dst + ((u64)b * P.dstride + inner);
+    }
+    const TowerConst tc = P.tc[t];
+    const u64 q = tc.q;
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
+    const u64* tw = P.tw + (u64)t * N * 2;
+    const u32 L2 = h * 272 + r;  // lds_pad(256 h + r + 16 k) = L2 + 17 k
+    const u32 L3 = tid * 17;     // lds_pad(16 tid + k)       = L3 + k
+    u64 v[QP][16];
+
+#pragma unroll
+    for (int s = 0; s < QP; s++)
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[s][k] = ld_s(blk[s] + r + 16 * k);
+    fwd_round16(v, tw, (N >> 8) + g, M);  // wave-uniform twiddles: scalar loads
+#pragma unroll
+    for (int s = 0; s < QP; s++) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[L2 + 17 * k] = v[s][k];
+        __builtin_amdgcn_wave_barrier();
+        // round 3: words 16 r + k of the team's group
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[s][k] = lds[L3 + k];
+        __builtin_amdgcn_wave_barrier();  // the next set's writes stay behind these reads
+    }
+    // early loads of the Hadamard operand (block_body): all eight of each set
+    // where the 168 VGPRs hold them (special primes), else three (generic
+    // moduli: eight spilled 9 VGPRs)
+    constexpr int BPF = SPQ ? OFHE_B_PF : 3;
+    u64x2 bpre[QP][BPF > 0 ? BPF : 1];
+#pragma unroll
+    for (int s = 0; s < QP; s++)
+#pragma unroll
+        for (int k = 0; k < BPF; k++) bpre[s][k] = ld2_s(bdat + boff[s] + StageMap<true>(tid).g(k));
+    {
+        const u64* tw3 = P.tw3 + (u64)t * (N / 16) * 30;
+        const u32 U = N >> 4, u = g * 16 + r;
+        fwd_stage16_t3<0>(v, tw3, U, u, M);
+        fwd_stage16_t3<1>(v, tw3, U, u, M);
+        fwd_stage16_t3<2>(v, tw3, U, u, M);
+        fwd_stage16_t3<3>(v, tw3, U, u, M);
+    }
+    // Hadamard, a Montgomery product on the lazy forward output (< 12q): one
+    // set's operand at a time through the wave's slots (wave_stage_in_pre ends
+    // with the fence the next set's writes need)
+#pragma unroll
+    for (int s = 0; s < QP; s++) {
+        u64 bb[16];
+        wave_stage_in_pre<true, BPF>(bdat + boff[s], lds, tid, bpre[s], bb);
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[s][k] = mont_mul(v[s][k], bb[k], q, tc.qinv);  // (0, 2q)
+    }
+    const u64* dtw = P.dtw + (u64)t * N * 2;
+    dit_round3(v, dtw, M);
+#pragma unroll
+    for (int s = 0; s < QP; s++) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[L3 + k] = v[s][k];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[s][k] = lds[L2 + 17 * k];
+        __builtin_amdgcn_wave_barrier();  // the next set's writes stay behind these reads
+    }
+    dit_round16(v, dtw, 16, r, M);
+    // twist into the GS column pass's input, lazy [0, 4q).  The compiler sinks
+    // a set's products into its store region, so the entries fetched together
+    // stay live until the last set's region: four at a time (16 VGPRs; with
+    // all sixteen the kernels spilled 41 to 76 VGPRs)
+    const u64* tw_ = P.twist + (u64)t * N * 2 + 2 * ((u64)g << 8);
+    constexpr int TG = 4;
+#pragma unroll
+    for (int k0 = 0; k0 < 16; k0 += TG) {
+#pragma unroll
+        for (int k = k0; k < k0 + TG; k++) {
+            const Tw f = ldtw(tw_, r + 16 * k);
+#pragma unroll
+            for (int s = 0; s < QP; s++) v[s][k] = shoup_lazy(v[s][k], f.w, f.wp, M);
+        }
+#pragma unroll
+        for (int s = 0; s < QP; s++) {
+            if (live[s]) {  // one divergent region for the TG stores
+#pragma unroll
+                for (int k = k0; k < k0 + TG; k++) st_s(oblk[s] + r + 16 * k, v[s][k]);
+            }
+        }
+    }
+}
+// QP = 2 (block_body_q2) holds two sets of registers: three workgroups (waves
+// per SIMD) per CU, at most 168 VGPRs
+template <int MODE, bool SPQ, int NR, int SK = 0, int QP = 1>
+__global__ __launch_bounds__(256, QP == 2 ? 3 : OFHE_KB_WAVES) void k_block(PlanArgs P, const u64* src, u64* dst,
+                                                                            const u64* __restrict__ bdat, u32 batch,
+                                                                            u32 nwg) {
+    static_assert(QP == 1 || (QP == 2 && NR == 2 && MODE == MODE_FUSED), "k_block: QP = 2 is the fused NR = 2 pass");
     OFHE_VGPR_FLOOR();
     __shared__ u64 lds[LDS_WORDS];
-    block_body<MODE, SPQ, NR, SK>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
+    if constexpr (QP == 2)
+        block_body_q2<SPQ>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
+    else
+        block_body<MODE, SPQ, NR, SK>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
 }
 
 // Rescaling source of the forward column pass (k_cols / k_tcols <.., SWS = true>):

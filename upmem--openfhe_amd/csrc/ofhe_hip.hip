@@ -591,11 +591,16 @@ static void launch_block(const PlanArgs& a, bool spq, const u64* src, u64* dst, 
         constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
         // one work item per 4096-element block (NR = 3), or per 1024 elements
         // of four consecutive polynomials of a tower (NR = 2, block_body): the
-        // same count when batch % 4 == 0
-        const u32 nwg = NR == 2 ? ((batch + 3) / 4) * a.towers * (1u << (a.log_n - 10))
-                                : batch * a.towers * (1u << (a.log_n - 12));
-        hipLaunchKernelGGL((k_block<MODE, decltype(sp)::value, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b,
-                           batch, nwg);
+        // same count when batch % 4 == 0.  The fused pipeline at N = 2^16 runs
+        // two such quads per thread (QP = 2: an octet of polynomials per item);
+        // the standalone modes and N = 2^17 keep one.
+        with_bool(NR == 2 && MODE == MODE_FUSED && a.log_n == 16, [&](auto oct) {
+            constexpr int QP = (NR == 2 && MODE == MODE_FUSED && decltype(oct)::value) ? 2 : 1;
+            const u32 nwg = NR == 2 ? ((batch + 4 * QP - 1) / (4 * QP)) * a.towers * (1u << (a.log_n - 10))
+                                    : batch * a.towers * (1u << (a.log_n - 12));
+            hipLaunchKernelGGL((k_block<MODE, decltype(sp)::value, NR, SK, QP>), dim3(nwg), dim3(256), 0, s, a, src,
+                               dst, b, batch, nwg);
+        });
     }); });
 }
 
