@@ -436,6 +436,43 @@ int ofhe_hip_ks_bsgs_transform(ofhe_ks_t ks, uint32_t size_ql, const ofhe_bsgs* 
                                const uint64_t* c1, uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch,
                                void* stream);
 
+/* ---- CKKS / BGV multiplication with relinearisation and rescaling ----
+ * LeveledSHEBase::EvalMult(ct1, ct2, evalKey) and its InPlace / Mutable forms (base-leveledshe.cpp:199-259,
+ * 322-338), EvalSquare(ct, evalKey) and its forms (262-319), EvalMultCore (657-696), EvalSquareCore (699-750),
+ * Relinearize / RelinearizeInPlace / EvalMultAndRelinearize (341-372),
+ * LeveledSHECKKSRNS::ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132) and
+ * LeveledSHEBGVRNS::ModReduceInternalInPlace (bgvrns-leveledshe.cpp:45-77), on the HYBRID engine.  All
+ * polynomials are in evaluation form, [batch][towers][N] dense, over the engine's q[0..size_ql), 16-byte aligned.
+ * The rescaling tables (qlInvModq, QlQlInvModqlDivqlModq, negtInvModq: ckksrns-cryptoparameters.cpp:66-87,
+ * bgvrns-cryptoparameters.cpp:91-107) are built by the engine from its moduli.
+ * scheme: OFHE_SHE_CKKS rescales by DropLastElementAndScale, t must be 0; OFHE_SHE_BGV rescales by ModReduce,
+ * t >= 2 and invertible modulo every tower it meets (the same t goes to the key switch's ModDown).
+ * The rescale the AUTO scaling techniques apply to an operand before the product (rns-leveledshe.cpp:172-216)
+ * is the caller's ofhe_hip_ks_rescale on that operand; scaling factors and noise degrees stay with the caller. */
+#define OFHE_SHE_CKKS 0
+#define OFHE_SHE_BGV 1
+
+/* ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77): `levels` >= 1 rescalings of a ciphertext of nelem >= 1 elements,
+ * x[k] over size_ql towers -> out[k] over size_ql - levels >= 1 towers. x / out: host arrays of device pointers.
+ * No output may overlap an input or another output. */
+int ofhe_hip_ks_rescale(ofhe_ks_t ks, uint32_t size_ql, int scheme, uint64_t t, uint32_t levels, uint32_t nelem,
+                        const uint64_t* const* x, uint64_t* const* out, uint32_t batch, void* stream);
+
+/* RelinearizeInPlace (base-leveledshe.cpp:357-372) of nelem >= 3 elements: for j >= 2, ab = KeySwitchCore(c[j], key[j-2]); out0 = c[0] + sum ab[0],
+ * out1 = c[1] + sum ab[1]. key_b / key_a: host arrays of nelem - 2 device pointers, keys laid out as for ofhe_hip_ks_core.
+ * out0 may be c[0] and out1 may be c[1]; no other overlap. t as for ofhe_hip_ks_core. */
+int ofhe_hip_ks_relinearize(ofhe_ks_t ks, uint32_t size_ql, uint32_t nelem, const uint64_t* const* c,
+                            const uint64_t* const* key_b, const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1,
+                            uint64_t t, uint32_t batch, void* stream);
+
+/* EvalMult(ct1, ct2, evalKey) (base-leveledshe.cpp:199-218) then ModReduceInternalInPlace(levels), levels >= 0.
+ * d0 == d1 == NULL: EvalSquare(ct, evalKey) (262-280).
+ * out0, out1 over size_ql - levels towers. An output may start exactly at an operand's address (the InPlace
+ * forms: the tensor product consumes the operands first); any other overlap is refused. */
+int ofhe_hip_ks_eval_mult(ofhe_ks_t ks, uint32_t size_ql, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
+                          const uint64_t* d1, const uint64_t* key_b, const uint64_t* key_a, int scheme, uint64_t t,
+                          uint32_t levels, uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream);
+
 /* ---- element maps ---- */
 /* NativeVectorT::SwitchModulus (mubintvecnat.cpp:111-136) on n words:
  * values of modulus old_q re-centred to new_q, exactly as the reference. */

@@ -14,8 +14,18 @@ ordinal is dropped (in labels and in the loop comments that cite them, with
 the padding that aligns a label's comment); so are the __hip_cuid_ lines, a
 hash of the source text, and the .section line that closes a function's text
 by naming the next function.
-What lies outside any function is compared as "(file scope)".  Exit status 1
-when a kernel differs or exists only in the second tree.
+What lies outside any function is compared as "(file scope)"; the file's
+trailer (the code-end padding after the last function and what follows it, the
+target and version lines after the last metadata entry) belongs to no kernel
+and is left out, so a kernel does not change by ceasing to be the file's last.
+Exit status 1 when a kernel differs or exists only in the second tree.
+
+A change that adds kernels names them: `--new REGEX` (repeatable) lists the
+kernels that exist only in the second tree and whose mangled name matches as
+"new", without counting them:
+
+    python tools/isa_diff.py PARENT_CSRC upmem--openfhe_amd/csrc \\
+        --new 'k_block_add|k_sub_scale_add|k_square2'
 
 A template that gained a defaulted parameter keeps its code and changes its
 mangled name; `--rename REGEX REPL` (repeatable) rewrites the first tree's
@@ -38,6 +48,7 @@ BEGIN = re.compile(r"; -- Begin function (\S+)")  # on the symbol's .globl or .w
 OBJECT = re.compile(r"^\s*\.type\s+\S+,@object")
 NEXT_SECTION = re.compile(r"^\s*\.section\s+\.text\.")  # ends a function's text and names the next function
 PAD = re.compile(r"\s+;")  # a label's comment is aligned by the label's length, ordinal included
+CODE_END = re.compile(r"^\s*\.p2alignl\b")  # the padding after the file's last function; a .text line precedes it
 ORDINAL = re.compile(r"(\.L(?:BB|func_(?:begin|end)|JTI|tmp|CPI)|\bBB(?=\d+_\d))\d+")  # BBn_m: loop comments
 
 
@@ -58,10 +69,15 @@ def assembly(csrc, src):
 def kernels(text):
     """{mangled name: text} of one assembly file, plus "(file scope)"."""
     text, _, meta = text.partition("amdhsa.kernels:\n")
+    meta = meta.partition("\namdhsa.target:")[0]
     parts, name = {"(file scope)": []}, "(file scope)"
     for line in text.splitlines():
         if "__hip_cuid_" in line or NEXT_SECTION.match(line):
             continue
+        if CODE_END.match(line):
+            if parts[name] and parts[name][-1].strip() == ".text":
+                parts[name].pop()
+            break
         m = BEGIN.search(line)
         if m:
             name = m.group(1)
@@ -76,7 +92,7 @@ def kernels(text):
     return {k: "\n".join(v) for k, v in parts.items()}
 
 
-def main(a, b, renames=()):
+def main(a, b, renames=(), new=()):
     srcs = make_var("SRCS").split()
     with ThreadPoolExecutor(os.cpu_count() or 1) as pool:
         texts = list(pool.map(lambda job: assembly(*job), [(d, s) for s in srcs for d in (a, b)]))
@@ -87,11 +103,14 @@ def main(a, b, renames=()):
     for i, src in enumerate(srcs):
         ka, kb = kernels(texts[2 * i]), kernels(texts[2 * i + 1])
         only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
+        named = [k for k in only_b if any(re.search(n, k) for n in new)]
+        only_b = [k for k in only_b if k not in named]
         differ = sorted(k for k in set(ka) & set(kb) if ka[k] != kb[k])
         print(f"{src}: {len(ka) - 1} and {len(kb) - 1} functions; with the file scope "
               f"{len(set(ka) & set(kb)) - len(differ)} identical, "
               f"{len(differ)} differ, {len(only_a)} only in the first tree, {len(only_b)} only in the second")
-        for tag, names in (("differs", differ), ("only in first", only_a), ("only in second", only_b)):
+        for tag, names in (("differs", differ), ("only in first", only_a), ("only in second", only_b),
+                           ("new", named)):
             for k in names:
                 print(f"  {tag}: {k}")
         bad += len(differ) + len(only_b)
@@ -99,9 +118,13 @@ def main(a, b, renames=()):
 
 
 if __name__ == "__main__":
-    args, renames = sys.argv[1:], []
+    args, renames, new = sys.argv[1:], [], []
     while "--rename" in args:
         i = args.index("--rename")
         renames.append((args[i + 1], args[i + 2]))
         del args[i:i + 3]
-    sys.exit(main(os.path.abspath(args[0]), os.path.abspath(args[1]), renames))
+    while "--new" in args:
+        i = args.index("--new")
+        new.append(args[i + 1])
+        del args[i:i + 2]
+    sys.exit(main(os.path.abspath(args[0]), os.path.abspath(args[1]), renames, new))

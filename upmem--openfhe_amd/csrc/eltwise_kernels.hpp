@@ -54,6 +54,33 @@ __global__ __launch_bounds__(256) void k_tensor2(const TowerConst* __restrict__ 
     st2_s(o2 + e, r2);
 }
 
+// LeveledSHEBase::EvalSquareCore for a 2-element ciphertext
+// (base-leveledshe.cpp:707-713): o0 = c0 c0, o1 = c0 c1 + c0 c1, o2 = c1 c1,
+// the products and the sum as k_tensor2's, whose words for (c, c) these are:
+// 16 B read and 24 B written per coefficient.  Rows and pairs as k_tensor2.
+template <int V = 0>
+__global__ __launch_bounds__(256) void k_square2(const TowerConst* __restrict__ tcs, const u64* c0, const u64* c1,
+                                                 u64* o0, u64* o1, u64* o2, u32 bpr, u32 log_n, u32 towers) {
+    OFHE_VGPR_FLOOR();
+    const u32 row = blockIdx.x / bpr;
+    const u64 j = 2 * ((u64)(blockIdx.x % bpr) * blockDim.x + threadIdx.x);
+    if (j >= (1ull << log_n)) return;
+    const u64 e = ((u64)row << log_n) + j;
+    const TowerConst tc = tcs[row % towers];
+    const u64x2 a0 = ld2_s(c0 + e), a1 = ld2_s(c1 + e);
+    u64x2 r0, r1, r2;
+    r2.x = barrett_ref(a1.x, a1.x, tc.q, tc.mu, tc.nshift);
+    r2.y = barrett_ref(a1.y, a1.y, tc.q, tc.mu, tc.nshift);
+    const u64 mx = barrett_ref(a1.x, a0.x, tc.q, tc.mu, tc.nshift), my = barrett_ref(a1.y, a0.y, tc.q, tc.mu, tc.nshift);
+    r1.x = modadd_fast(mx, mx, tc.q);
+    r1.y = modadd_fast(my, my, tc.q);
+    r0.x = barrett_ref(a0.x, a0.x, tc.q, tc.mu, tc.nshift);
+    r0.y = barrett_ref(a0.y, a0.y, tc.q, tc.mu, tc.nshift);
+    st2_s(o0 + e, r0);
+    st2_s(o1 + e, r1);
+    st2_s(o2 + e, r2);
+}
+
 template <int OP>
 __global__ __launch_bounds__(256) void k_eltwise(const TowerConst* __restrict__ tcs,
                                                  const u64* a, const u64* b, u64* c, u64 npairs,

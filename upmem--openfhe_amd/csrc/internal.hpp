@@ -2,7 +2,7 @@
 // (ofhe_hip.hip: context, plans, NTT, element-wise ops, tensor product, base
 // conversion (approximate and exact); keyswitch.hip: ApproxModUp /
 // ApproxModDown, hybrid key switching, hoisted rotations, the BSGS linear
-// transform, rescaling, BV key switching; bfv.hip: ExpandCRTBasis,
+// transform, rescaling, CKKS / BGV multiplication, BV key switching; bfv.hip: ExpandCRTBasis,
 // ScaleAndRound, BFV multiplication (HPS, HPSPOVERQ); bfv_leveled.hip:
 // HPSPOVERQLEVELED multiplication and relinearisation with dropped levels;
 // behz.hip: BFV multiplication (BEHZ); bfv_decrypt.hip: BFV decryption,
@@ -119,9 +119,10 @@ int plan_ntt_range(ofhe_plan_t p, bool inverse, u32 t0, u32 count, const u64* sr
 // pass) whose block pass writes out = (x - NTT(y)) * s_t mod q_t instead of
 // NTT(y); scal = device [count][3] (q, s, s').  log_n >= 12.  parts: 1 = the
 // column pass only, 2 = the block pass only (y already through the column
-// pass), 3 = both.
+// pass), 3 = both.  add != NULL: out = add + (x - NTT(y)) * s_t, add laid out as
+// out (batch stride ostride) and possibly out itself (k_block_add).
 int plan_ntt_fwd_sub(ofhe_plan_t p, u32 t0, u32 count, u64* y, u64 ystride, const u64* x, u64 xstride, u64* out,
-                     u64 ostride, const u64* scal, u32 batch, hipStream_t s, int parts = 3);
+                     u64 ostride, const u64* scal, u32 batch, hipStream_t s, int parts = 3, const u64* add = nullptr);
 
 // ApproxSwitchCRTBasis fused with the targets' forward column pass
 // (k_bconv_cols, bconv_cols.hpp): N = 2^17, SPLIT_COLS plans, <= 16 sources.
@@ -200,6 +201,12 @@ inline int cached_table(std::mutex& mu, std::map<Key, T*>& tabs, const Key& key,
     *out = it->second;
     return OFHE_OK;
 }
+
+// EvalMultCore of two 2-element ciphertexts over the first `towers` towers of p
+// (k_tensor2), or EvalSquareCore of (c0, c1) when d0 == d1 == NULL (k_square2):
+// dense [batch][towers][N] operands and products.
+int tensor2_run(ofhe_plan_t p, u32 towers, const u64* c0, const u64* c1, const u64* d0, const u64* d1, u64* out0,
+                u64* out1, u64* out2, u32 batch, hipStream_t s);
 
 // ApproxSwitchCRTBasis launch (strides and output gap from A)
 int bconv_run(const BconvArgs& A, const u64* x, u64* out, u32 batch, hipStream_t s);

@@ -8,6 +8,9 @@
 //   KeySwitchHYBRID::EvalKeySwitchPrecomputeCore  keyswitch-hybrid.cpp:330-412
 //   KeySwitchHYBRID::EvalFastKeySwitchCoreExt     keyswitch-hybrid.cpp:438-482
 //   KeySwitchHYBRID::EvalFastKeySwitchCore        keyswitch-hybrid.cpp:414-436
+//   LeveledSHEBase::EvalMult / EvalSquare / Relinearize (with evaluation keys)
+//                                                 base-leveledshe.cpp:199-372
+//   ModReduceInternalInPlace   ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77
 // CRT tables follow CryptoParametersRNS::PrecomputeCRTTables
 // (rns-cryptoparameters.cpp:72-345).  The reference builds them with
 // BigInteger quotients (Q/q_i) and reductions; every table entry is a residue
@@ -54,10 +57,14 @@ int scale_towers(const TowerScalar* d, const u64* x, u64* out, u64 xs, u64 os, u
 }
 
 int sub_scale(const TowerScalar* d, const u64* x, const u64* y, u64* out, u64 xs, u64 ys, u64 os, u32 batch,
-              u32 towers, u32 log_n, hipStream_t s) {
+              u32 towers, u32 log_n, hipStream_t s, const u64* add = nullptr) {
     const u64 npairs = ((u64)batch * towers << log_n) / 2;
-    hipLaunchKernelGGL(k_sub_scale, dim3(grid_for(npairs)), dim3(256), 0, s, d, x, y, out, xs, ys, os, npairs,
-                       log_n, towers);
+    if (add)
+        hipLaunchKernelGGL(k_sub_scale_add, dim3(grid_for(npairs)), dim3(256), 0, s, d, x, y, add, out, xs, ys, os,
+                           npairs, log_n, towers);
+    else
+        hipLaunchKernelGGL(k_sub_scale, dim3(grid_for(npairs)), dim3(256), 0, s, d, x, y, out, xs, ys, os, npairs,
+                           log_n, towers);
     return post_launch();
 }
 
@@ -84,9 +91,11 @@ static bool md_icol(const ModDownArgs& A) {
 // input k starts at x + k * batch * xstride (KeySwitchCore's ct1 follows its
 // ct0), so the P-part INTT, the base conversion and the column pass run once
 // over nout * batch polynomials; only the last pass, which writes the caller's
-// out[k], runs per output.
+// out[k], runs per output.  add != NULL: out[k] = add[k] + that (add[k] laid
+// out as out[k], and possibly out[k] itself): the sums of a relinearisation
+// (base-leveledshe.cpp:212-213, 368-369) taken in the last pass.
 int mod_down_run(const ModDownArgs& A, const u64* x, u64 xstride, u64* const* out, u32 nout, u64 ostride, u32 batch,
-                 hipStream_t s) {
+                 hipStream_t s, const u64* const* add = nullptr) {
     const u32 log_n = A.plan_q->log_n;
     const u64 N = 1ull << log_n;
     const u32 bn = nout * batch;
@@ -128,9 +137,11 @@ int mod_down_run(const ModDownArgs& A, const u64* x, u64 xstride, u64* const* ou
         const u64* xk = x + (u64)k * batch * xstride;
         u64* sqk = sq.w() + (u64)k * batch * qs;
         if (block_tail)
-            RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sqk, qs, xk, xstride, out[k], ostride, pinv, batch, s, 2));
+            RCCHK(plan_ntt_fwd_sub(A.plan_q, A.q0, A.size_q, sqk, qs, xk, xstride, out[k], ostride, pinv, batch, s, 2,
+                                   add ? add[k] : nullptr));
         else
-            RCCHK(sub_scale(A.pinv, xk, sqk, out[k], xstride, qs, ostride, batch, A.size_q, log_n, s));
+            RCCHK(sub_scale(A.pinv, xk, sqk, out[k], xstride, qs, ostride, batch, A.size_q, log_n, s,
+                            add ? add[k] : nullptr));
     }
     return OFHE_OK;
 }
@@ -212,6 +223,11 @@ struct KsLevel {
     std::map<u64, TowerScalar*> tscale; // t -> [size_p] t^-1 mod p_j, then [size_ql] t mod q_i
 };
 
+struct RsTab {
+    std::vector<u64> sw, sc;
+    u64 pre = 1;
+};
+
 struct ofhe_ks_s {
     ofhe_ctx_t ctx = nullptr;
     u32 log_n = 0, size_q = 0, size_p = 0, num_part_q = 0, alpha = 0;
@@ -223,6 +239,9 @@ struct ofhe_ks_s {
     bool icol = true;                 // ... with the INTT's column pass inside it (options.separate_icol: off)
     std::mutex mu;
     std::map<u32, KsLevel*> levels;
+    // rescaling tables for dropping tower `towers - 1`, keyed by (towers, t) with t = 0 for CKKS:
+    // rescale_run's sw / sc words and ModReduce's negtInvModq (rs_tables)
+    std::map<std::pair<u32, u64>, RsTab> rescale;
 };
 
 static void level_free(KsLevel* L) {
@@ -593,13 +612,9 @@ int ofhe_hip_ks_mod_down(ofhe_ks_t k, uint32_t size_ql, const uint64_t* x, uint6
     return ks_mod_down_impl(k, L, x, out, t, batch, pick(stream));
 }
 
-int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uint64_t* key_b, const uint64_t* key_a,
-                     uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch, void* stream) {
-    RCCHK(ks_check(k, size_ql, batch));
-    if (!c || !key_b || !key_a || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
-    KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
-    hipStream_t s = pick(stream);
+// KeySwitchCore of c into out0 / out1, plus add0 / add1 when given (mod_down_run)
+static int ks_core_impl(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* c, const u64* key_b, const u64* key_a,
+                        u64* out0, u64* out1, const u64* add0, const u64* add1, u64 t, u32 batch, hipStream_t s) {
     const u64 N = 1ull << k->log_n, poly = (u64)(size_ql + k->size_p) * N;
     Scratch dg, ct;
     RCCHK(dg.alloc((size_t)batch * L->beta * poly * 8, s, k->ctx));
@@ -615,7 +630,17 @@ int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uin
     ModDownArgs A;
     RCCHK(ks_md_args(k, L, t, &A));
     u64* const outs[2] = {out0, out1};
-    return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s);
+    const u64* const adds[2] = {add0, add1};
+    return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s, add0 ? adds : nullptr);
+}
+
+int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uint64_t* key_b, const uint64_t* key_a,
+                     uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch, void* stream) {
+    RCCHK(ks_check(k, size_ql, batch));
+    if (!c || !key_b || !key_a || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    return ks_core_impl(k, L, size_ql, c, key_b, key_a, out0, out1, nullptr, nullptr, t, batch, pick(stream));
 }
 
 // ---------------------------------------------------------------------------
@@ -1066,10 +1091,17 @@ static int rescale_check(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, const 
 }
 
 // shared tail: sw[6 L] for k_switch_scale, sc[3 L] (q, a, a') for the
-// forward-subtract (evaluation form)
-static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out, u64 os, bool eval, int mode,
-                       const std::vector<u64>& sw, const std::vector<u64>& sc, u64 pre, u32 batch, hipStream_t s) {
+// forward-subtract (evaluation form).  nelem elements x[e] -> out[e] of `batch`
+// entries each (evaluation form when nelem > 1): the last towers' INTT (one
+// launch when the elements follow one another), the lift and the column pass
+// run over nelem * batch polynomials, the pass that writes out[e] per element.
+static int rescale_run(ofhe_plan_t p, u32 towers, const u64* const* xv, u64 xs, u64* const* outv, u64 os, u32 nelem,
+                       bool eval, int mode, const std::vector<u64>& sw, const std::vector<u64>& sc, u64 pre,
+                       u32 batch, hipStream_t s) {
     HIPCHK(hipSetDevice(p->ctx->device));
+    const u64* x = xv[0];
+    u64* out = outv[0];
+    const u32 bn = nelem * batch;
     const u32 L = towers - 1, log_n = p->log_n;
     const u64 N = 1ull << log_n;
     const u64 *dsw = nullptr, *dsc = nullptr;
@@ -1086,7 +1118,7 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
     A.towers = L;
     const u32 bpr = (u32)((N / 2 + 255) / 256);  // two coefficients per thread
     dim3 g;
-    RCCHK(coeff_grid((u64)bpr * batch * L * 256, &g, "batch too large for one launch"));
+    RCCHK(coeff_grid((u64)bpr * bn * L * 256, &g, "batch too large for one launch"));
     if (!eval) {
         A.last = x + (u64)L * N;
         A.lstride = xs;
@@ -1104,15 +1136,33 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
         return OFHE_OK;
     }
     Scratch sl, sy;
-    RCCHK(sl.alloc((size_t)batch * N * 8, s, p->ctx));
-    RCCHK(sy.alloc((size_t)batch * L * N * 8, s, p->ctx));
-    RCCHK(plan_ntt_range(p, true, L, 1, x + (u64)L * N, sl.w(), xs, N, batch, s));
+    RCCHK(sl.alloc((size_t)bn * N * 8, s, p->ctx));
+    RCCHK(sy.alloc((size_t)bn * L * N * 8, s, p->ctx));
+    bool dense = true;  // element e + 1 follows element e
+    for (u32 e = 1; e < nelem; e++) dense = dense && xv[e] == x + (u64)e * batch * xs;
+    if (dense)
+        RCCHK(plan_ntt_range(p, true, L, 1, x + (u64)L * N, sl.w(), xs, N, bn, s));
+    else
+        for (u32 e = 0; e < nelem; e++)
+            RCCHK(plan_ntt_range(p, true, L, 1, xv[e] + (u64)L * N, sl.w() + (u64)e * batch * N, xs, N, batch, s));
     const u64 ys = (u64)L * N;
+    // the per-element tail: the forward-subtract block pass (log_n >= 12), or k_sub_scale
+    auto tail = [&](bool block) {
+        for (u32 e = 0; e < nelem; e++) {
+            u64* ye = sy.w() + (u64)e * batch * ys;
+            if (block)
+                RCCHK(plan_ntt_fwd_sub(p, 0, L, ye, ys, xv[e], xs, outv[e], os, dsc, batch, s, 2));
+            else
+                RCCHK(sub_scale(reinterpret_cast<const TowerScalar*>(dsc), xv[e], ye, outv[e], xs, ys, os, batch, L,
+                                log_n, s));
+        }
+        return (int)OFHE_OK;
+    };
     if (log_n > 12 && p->split != SPLIT_T9) {
         // the lift happens in the column pass's loads (k_cols<.., SWS>): the
         // switched towers are never written to HBM before their transform
-        RCCHK(plan_cols_switch(p, 0, L, sl.w(), N, ql, A.pre, dsw, sy.w(), ys, batch, s));
-        return plan_ntt_fwd_sub(p, 0, L, sy.w(), ys, x, xs, out, os, dsc, batch, s, 2);
+        RCCHK(plan_cols_switch(p, 0, L, sl.w(), N, ql, A.pre, dsw, sy.w(), ys, bn, s));
+        return tail(true);
     }
     A.last = sl.w();
     A.lstride = N;
@@ -1120,9 +1170,12 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, u64* out
     A.ystride = ys;
     hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, g, dim3(256), 0, s, A, bpr);
     RCCHK(post_launch());
-    if (log_n >= 12) return plan_ntt_fwd_sub(p, 0, L, sy.w(), ys, x, xs, out, os, dsc, batch, s);
-    RCCHK(plan_ntt_range(p, false, 0, L, sy.w(), sy.w(), ys, ys, batch, s));
-    return sub_scale(reinterpret_cast<const TowerScalar*>(dsc), x, sy.w(), out, xs, ys, os, batch, L, log_n, s);
+    if (log_n >= 12) {
+        RCCHK(plan_ntt_fwd_sub(p, 0, L, sy.w(), ys, x, xs, out, os, dsc, bn, s, 1));  // the column pass (log_n > 12)
+        return tail(true);
+    }
+    RCCHK(plan_ntt_range(p, false, 0, L, sy.w(), sy.w(), ys, ys, bn, s));
+    return tail(false);
 }
 
 int ofhe_hip_drop_last_and_scale(ofhe_plan_t p, uint32_t towers, const uint64_t* x, uint64_t x_stride,
@@ -1146,7 +1199,7 @@ int ofhe_hip_drop_last_and_scale(ofhe_plan_t p, uint32_t towers, const uint64_t*
             sw[6 * i] = q, sw[6 * i + 1] = W.s, sw[6 * i + 2] = W.sp, sw[6 * i + 3] = S.s, sw[6 * i + 4] = S.sp;
         }
     }
-    return rescale_run(p, towers, x, x_stride, out, out_stride, eval_form != 0, SW_AXPY, sw, sc, 1, batch,
+    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, SW_AXPY, sw, sc, 1, batch,
                        pick(stream));
 }
 
@@ -1163,8 +1216,8 @@ int ofhe_hip_mod_reduce(ofhe_plan_t p, uint32_t towers, const uint64_t* x, uint6
         sw[6 * i] = q, sw[6 * i + 1] = W.s, sw[6 * i + 2] = W.sp, sw[6 * i + 3] = S.s, sw[6 * i + 4] = S.sp;
         sc[3 * i] = q, sc[3 * i + 1] = S.s, sc[3 * i + 2] = S.sp;
     }
-    return rescale_run(p, towers, x, x_stride, out, out_stride, eval_form != 0, SW_XPYA, sw, sc, neg_t_inv_modq,
-                       batch, pick(stream));
+    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, SW_XPYA, sw, sc,
+                       neg_t_inv_modq, batch, pick(stream));
 }
 
 // ---------------------------------------------------------------------------
@@ -1246,4 +1299,198 @@ int ofhe_hip_bv_core(ofhe_plan_t p, uint32_t towers, const uint64_t* digits, con
     RCCHK(coeff_grid((u64)bpr * batch * towers * 256, &g, "batch too large for one launch"));
     hipLaunchKernelGGL(k_bv_inner, g, dim3(256), 0, pick(stream), A, bpr);
     return post_launch();
+}
+
+// ---------------------------------------------------------------------------
+// CKKS / BGV multiplication on the HYBRID engine: EvalMult / EvalSquare with
+// relinearisation (base-leveledshe.cpp:199-338, cores 657-750), Relinearize
+// (341-372) and ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132,
+// bgvrns-leveledshe.cpp:45-77), composed from the tensor product, the key
+// switch (whose ModDown takes the sums c0 + ab[0], c1 + ab[1] in its last pass)
+// and rescale_run.  The rescaling tables come from the engine's moduli.
+// ---------------------------------------------------------------------------
+// Tables for dropping tower l = towers - 1 (ckksrns-cryptoparameters.cpp:66-87,
+// bgvrns-cryptoparameters.cpp:91-107): a_i = qlInvModq[i] = q_l^-1 mod q_i;
+// BGV: negtInvModq = -t^-1 mod q_l; CKKS: QlQlInvModqlDivqlModq[i] = q_i - a_i.
+// With Q = prod_{j<l} q_j and b = Q^-1 mod q_l, b Q = 1 + k q_l and the table is
+// k = floor(b Q / q_l) mod q_i; Q = 0 mod q_i gives k q_l = -1, k = -a_i.
+// The words are those ofhe_hip_drop_last_and_scale / ofhe_hip_mod_reduce build
+// from the caller's constants (evaluation form).
+static int rs_tables(ofhe_ks_t k, u32 towers, u64 t, const RsTab** out) {
+    std::lock_guard<std::mutex> lk(k->mu);
+    const auto key = std::make_pair(towers, t);
+    auto it = k->rescale.find(key);
+    if (it == k->rescale.end()) {
+        const u32 L = towers - 1;
+        const u64 ql = k->q[L];
+        RsTab T;
+        T.sw.assign(6 * (size_t)L, 0);
+        T.sc.assign(3 * (size_t)L, 0);
+        for (u32 i = 0; i < L; i++) {
+            const u64 q = k->q[i], a = invmod(ql % q, q);
+            u64 w;
+            if (t)
+                w = (q - t % q) % q;
+            else  // -(c a^-1) with c = q - a and a^-1 = q_l mod q_i
+                w = (q - mulmod(q - a, ql % q, q)) % q;
+            const TowerScalar W = scalar_of(q, w), S = scalar_of(q, a);
+            T.sw[6 * i] = q, T.sw[6 * i + 1] = W.s, T.sw[6 * i + 2] = W.sp;
+            if (t) T.sw[6 * i + 3] = S.s, T.sw[6 * i + 4] = S.sp;
+            T.sc[3 * i] = q, T.sc[3 * i + 1] = S.s, T.sc[3 * i + 2] = S.sp;
+        }
+        T.pre = t ? ql - invmod(t % ql, ql) : 1;
+        it = k->rescale.emplace(key, std::move(T)).first;
+    }
+    *out = &it->second;
+    return OFHE_OK;
+}
+
+static int she_scheme_check(int scheme, u64 t) {
+    if (scheme != OFHE_SHE_CKKS && scheme != OFHE_SHE_BGV) return fail(OFHE_ERR_ARG, "scheme must be OFHE_SHE_CKKS or OFHE_SHE_BGV");
+    if (scheme == OFHE_SHE_CKKS && t != 0) return fail(OFHE_ERR_ARG, "OFHE_SHE_CKKS takes t = 0");
+    if (scheme == OFHE_SHE_BGV && t < 2) return fail(OFHE_ERR_ARG, "OFHE_SHE_BGV needs a plaintext modulus t >= 2");
+    return OFHE_OK;
+}
+
+// t (non-zero) is invertible modulo q[0..size_ql) and, with_p, modulo every p (the moduli are prime)
+static int she_t_check(ofhe_ks_t k, u32 size_ql, u64 t, bool with_p) {
+    if (!t) return OFHE_OK;
+    for (u32 i = 0; i < size_ql; i++)
+        if (t % k->q[i] == 0)
+            return fail(OFHE_ERR_ARG, "t is not invertible modulo tower q[" + std::to_string(i) + "]");
+    for (u32 j = 0; with_p && j < k->size_p; j++)
+        if (t % k->p[j] == 0)
+            return fail(OFHE_ERR_ARG, "t is not invertible modulo tower p[" + std::to_string(j) + "]");
+    return OFHE_OK;
+}
+
+static bool she_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// `levels` >= 1 rescalings, one after another in the reference's order, of nelem
+// elements x[e] (batch stride xs = l N) into out[e] (dense over l - levels towers);
+// the levels in between live in scratch, in place from the second on
+static int rescale_levels(ofhe_ks_t k, u32 l, int scheme, u64 t, u32 levels, u32 nelem, const u64* const* x,
+                          u64* const* out, u32 batch, hipStream_t s) {
+    const u64 N = 1ull << k->log_n;
+    std::vector<const RsTab*> tabs(levels);
+    for (u32 lv = 0; lv < levels; lv++) RCCHK(rs_tables(k, l - lv, scheme == OFHE_SHE_BGV ? t : 0, &tabs[lv]));
+    Scratch mid;
+    const u64 ms = (u64)(l - 1) * N;
+    if (levels > 1) RCCHK(mid.alloc((size_t)nelem * batch * ms * 8, s, k->ctx));
+    std::vector<const u64*> cur(x, x + nelem);
+    std::vector<u64*> nxt(nelem);
+    u64 cs = (u64)l * N;
+    for (u32 lv = 0; lv < levels; lv++) {
+        const bool last = lv + 1 == levels;
+        const u64 os = last ? (u64)(l - levels) * N : ms;
+        for (u32 e = 0; e < nelem; e++) nxt[e] = last ? out[e] : mid.w() + (u64)e * batch * ms;
+        RCCHK(rescale_run(k->plan, l - lv, cur.data(), cs, nxt.data(), os, nelem, true,
+                          scheme == OFHE_SHE_BGV ? SW_XPYA : SW_AXPY, tabs[lv]->sw, tabs[lv]->sc, tabs[lv]->pre, batch,
+                          s));
+        cur.assign(nxt.begin(), nxt.end());
+        cs = os;
+    }
+    return OFHE_OK;
+}
+
+int ofhe_hip_ks_rescale(ofhe_ks_t k, uint32_t size_ql, int scheme, uint64_t t, uint32_t levels, uint32_t nelem,
+                        const uint64_t* const* x, uint64_t* const* out, uint32_t batch, void* stream) {
+    // the checks that need no engine first, then the engine, then those that need its dimensions
+    if (!x || !out) return fail(OFHE_ERR_ARG, "NULL element pointer array");
+    if (nelem == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nelem and batch must be >= 1");
+    for (u32 e = 0; e < nelem; e++) {
+        if (!x[e] || !out[e]) return fail(OFHE_ERR_ARG, "NULL data pointer");
+        if (!she_aligned(x[e]) || !she_aligned(out[e])) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    }
+    RCCHK(she_scheme_check(scheme, t));
+    if (levels == 0) return fail(OFHE_ERR_ARG, "levels must be >= 1");
+    if (levels >= size_ql) return fail(OFHE_ERR_ARG, "levels must be below size_ql");
+    RCCHK(ks_check(k, size_ql, batch));
+    RCCHK(she_t_check(k, size_ql, t, false));
+    const u64 N = 1ull << k->log_n, xw = (u64)batch * size_ql * N, ow = (u64)batch * (size_ql - levels) * N;
+    for (u32 e = 0; e < nelem; e++) {
+        for (u32 j = 0; j < nelem; j++)
+            if (words_overlap(out[e], ow, x[j], xw) || (j != e && words_overlap(out[e], ow, out[j], ow)))
+                return fail(OFHE_ERR_ARG, "an output overlaps an input or another output");
+    }
+    return rescale_levels(k, size_ql, scheme, t, levels, nelem, x, out, batch, pick(stream));
+}
+
+int ofhe_hip_ks_relinearize(ofhe_ks_t k, uint32_t size_ql, uint32_t nelem, const uint64_t* const* c,
+                            const uint64_t* const* key_b, const uint64_t* const* key_a, uint64_t* out0,
+                            uint64_t* out1, uint64_t t, uint32_t batch, void* stream) {
+    if (!c || !key_b || !key_a) return fail(OFHE_ERR_ARG, "NULL element or key pointer array");
+    if (!out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (nelem < 3) return fail(OFHE_ERR_ARG, "relinearisation needs nelem >= 3 elements");
+    if (batch == 0) return fail(OFHE_ERR_ARG, "batch must be >= 1");
+    for (u32 j = 0; j < nelem; j++) {
+        if (!c[j]) return fail(OFHE_ERR_ARG, "NULL data pointer");
+        if (j >= 2 && (!key_b[j - 2] || !key_a[j - 2])) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
+        if (!she_aligned(c[j])) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    }
+    if (!she_aligned(out0) || !she_aligned(out1)) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    RCCHK(ks_check(k, size_ql, batch));
+    RCCHK(she_t_check(k, size_ql, t, true));
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    const u64 N = 1ull << k->log_n, w = (u64)batch * size_ql * N, kw = (u64)L->beta * (k->size_q + k->size_p) * N;
+    if (words_overlap(out0, w, out1, w)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    u64* const outs[2] = {out0, out1};
+    for (u32 o = 0; o < 2; o++) {
+        for (u32 j = 0; j < nelem; j++)
+            if (words_overlap(outs[o], w, c[j], w) && !(j == o && outs[o] == c[j]))
+                return fail(OFHE_ERR_ARG, "outputs may alias only their own element (out0 == c[0], out1 == c[1])");
+        for (u32 j = 0; j + 2 < nelem; j++)
+            if (words_overlap(outs[o], w, key_b[j], kw) || words_overlap(outs[o], w, key_a[j], kw))
+                return fail(OFHE_ERR_ARG, "outputs must not alias the keys");
+    }
+    // the second and later key switches add into the running output, in place
+    for (u32 j = 2; j < nelem; j++)
+        RCCHK(ks_core_impl(k, L, size_ql, c[j], key_b[j - 2], key_a[j - 2], out0, out1, j == 2 ? c[0] : out0,
+                           j == 2 ? c[1] : out1, t, batch, pick(stream)));
+    return OFHE_OK;
+}
+
+int ofhe_hip_ks_eval_mult(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
+                          const uint64_t* d1, const uint64_t* key_b, const uint64_t* key_a, int scheme, uint64_t t,
+                          uint32_t levels, uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream) {
+    if (!c0 || !c1 || !key_b || !key_a || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    if (!d0 != !d1) return fail(OFHE_ERR_ARG, "d0 and d1: both given (EvalMult) or both NULL (EvalSquare)");
+    if (batch == 0) return fail(OFHE_ERR_ARG, "batch must be >= 1");
+    for (const void* p : {(const void*)c0, (const void*)c1, (const void*)d0, (const void*)d1, (const void*)out0,
+                          (const void*)out1})
+        if (!she_aligned(p)) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    RCCHK(she_scheme_check(scheme, t));
+    if (levels >= size_ql) return fail(OFHE_ERR_ARG, "levels must be below size_ql");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    RCCHK(ks_check(k, size_ql, batch));
+    RCCHK(she_t_check(k, size_ql, t, true));
+    KsLevel* L = nullptr;
+    RCCHK(level_get(k, size_ql, &L));
+    const u32 l = size_ql;
+    const u64 N = 1ull << k->log_n, w = (u64)batch * l * N, ow = (u64)batch * (l - levels) * N;
+    const u64 kw = (u64)L->beta * (k->size_q + k->size_p) * N;
+    if (words_overlap(out0, ow, out1, ow)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    for (const u64* o : {out0, out1}) {
+        // the tensor product consumes the operands before anything is written: an
+        // output may start where an operand starts (the InPlace forms)
+        for (const u64* a : {c0, c1, d0, d1})
+            if (a && o != a && words_overlap(o, ow, a, w))
+                return fail(OFHE_ERR_ARG, "an output overlaps an operand without starting at its address");
+        if (words_overlap(o, ow, key_b, kw) || words_overlap(o, ow, key_a, kw))
+            return fail(OFHE_ERR_ARG, "outputs must not alias the keys");
+    }
+    if ((u64)((N / 2 + 255) / 256) * batch * l >= (1ull << 31))
+        return fail(OFHE_ERR_ARG, "batch too large for one launch");
+    hipStream_t s = pick(stream);
+    Scratch T;  // the three elements of the product, one after another
+    RCCHK(T.alloc((size_t)3 * w * 8, s, k->ctx));
+    u64 *T0 = T.w(), *T1 = T0 + w, *T2 = T1 + w;
+    RCCHK(tensor2_run(k->plan, l, c0, c1, d0, d1, T0, T1, T2, batch, s));
+    if (levels == 0) return ks_core_impl(k, L, l, T2, key_b, key_a, out0, out1, T0, T1, t, batch, s);
+    RCCHK(ks_core_impl(k, L, l, T2, key_b, key_a, T0, T1, T0, T1, t, batch, s));
+    const u64* const xs[2] = {T0, T1};
+    u64* const outs[2] = {out0, out1};
+    return rescale_levels(k, l, scheme, t, levels, 2, xs, outs, batch, s);
 }

@@ -63,6 +63,29 @@ __global__ __launch_bounds__(256) void k_sub_scale(const TowerScalar* __restrict
     }
 }
 
+// k_sub_scale plus an addend laid out as out (ModAddFastEq): the
+// relinearisation sums of base-leveledshe.cpp:352-360 in ApproxModDown's last
+// step.  add may be out itself: a thread reads the words it writes, first.
+__global__ __launch_bounds__(256) void k_sub_scale_add(const TowerScalar* __restrict__ ts, const u64* x, const u64* y,
+                                                       const u64* add, u64* out, u64 xstride, u64 ystride,
+                                                       u64 ostride, u64 npairs, u32 log_n, u32 towers) {
+    OFHE_VGPR_FLOOR();
+    const u64 step = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < npairs; i += step) {
+        const PairIndex p = pair_index(i, log_n, towers);
+        const TowerScalar c = ts[p.t];
+        const u64 inner = ((u64)p.t << log_n) + p.c;
+        const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(x + p.b * xstride + inner);
+        const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(y + p.b * ystride + inner);
+        const ulonglong2 e = *reinterpret_cast<const ulonglong2*>(add + p.b * ostride + inner);
+        const u64 d0 = a.x < b.x ? a.x + c.q - b.x : a.x - b.x;  // ModSubFastEq
+        const u64 d1 = a.y < b.y ? a.y + c.q - b.y : a.y - b.y;
+        *reinterpret_cast<ulonglong2*>(out + p.b * ostride + inner) =
+            make_ulonglong2(modadd_fast(e.x, shoup_canon(d0, c.s, c.sp, c.q), c.q),
+                            modadd_fast(e.y, shoup_canon(d1, c.s, c.sp, c.q), c.q));
+    }
+}
+
 // Tower of the extended basis Ql|P for the key-switch inner product.
 struct KsTower {
     u64 m;                // modulus

@@ -82,7 +82,10 @@ struct PlanArgs {
 // MODE_FWD_SUB: forward transform whose output is (x - NTT(y)) * s_t mod q,
 // the last step of ApproxModDown (dcrtpoly-impl.h:1167-1173) fused into the
 // block pass (x = bdat with batch stride bstride, (s, s') per tower in scal).
-enum { MODE_FWD = 0, MODE_INV = 1, MODE_FUSED = 2, MODE_FWD_SUB = 3 };
+// MODE_FWD_SUB_ADD: the same plus an addend laid out as the output,
+// out = add + (x - NTT(y)) * s_t mod q (k_block_add: the relinearisation sums
+// c0 + ab[0], c1 + ab[1] of base-leveledshe.cpp:352-360 inside the ModDown).
+enum { MODE_FWD = 0, MODE_INV = 1, MODE_FUSED = 2, MODE_FWD_SUB = 3, MODE_FWD_SUB_ADD = 4 };
 
 // Bijective XCD-aware block remap (cdna_hip_programming.md T1): consecutive
 // work items land on the same XCD.
@@ -640,7 +643,7 @@ __device__ __forceinline__ void block_sync() {
 }
 template <int MODE, bool SPQ, int NR, int SK = 0>
 __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u64* dst, const u64* __restrict__ bdat,
-                                           u32 batch, u32 wid, u64* lds, u32 tid) {
+                                           u32 batch, u32 wid, u64* lds, u32 tid, const u64* add = nullptr) {
     static_assert(NR == 2 || NR == 3, "k_block covers the last 8 (NR=2) or 12 (NR=3) stages");
     static_assert(SK == 0 || (SK == 3 && NR == 3), "k_block: SK = 3 needs NR = 3");
     constexpr bool TEAM = NR == 2;
@@ -682,7 +685,7 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
     const u32 L3 = tid * 17;     // lds_pad(16 tid + k)       = L3 + k
     u64 v[16];
 
-    if (MODE == MODE_FWD || MODE == MODE_FUSED || MODE == MODE_FWD_SUB) {
+    if (MODE == MODE_FWD || MODE == MODE_FUSED || MODE == MODE_FWD_SUB || MODE == MODE_FWD_SUB_ADD) {
         if (NR == 3) {
             // round 1: st = 256, p = tid + 256k
 #pragma unroll
@@ -713,7 +716,7 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
         // the first OFHE_B_PF of its 8 wave-coalesced 16-byte loads go out
         // now, so their HBM latency hides under round 3 (same-process A/B,
         // batch 256: fused block pass 1.740 -> 1.673 ms, VGPRs unchanged)
-        constexpr int BPF = (MODE == MODE_FUSED || MODE == MODE_FWD_SUB) ? OFHE_B_PF : 0;
+        constexpr int BPF = (MODE == MODE_FUSED || MODE == MODE_FWD_SUB || MODE == MODE_FWD_SUB_ADD) ? OFHE_B_PF : 0;
         u64x2 bpre[BPF > 0 ? BPF : 1];
 #pragma unroll
         for (int k = 0; k < BPF; k++) bpre[k] = ld2_s(bdat + boff + wq + StageMap<TEAM>(tid).g(k));
@@ -731,7 +734,7 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
             return;
         }
-        if (MODE == MODE_FWD_SUB) {
+        if (MODE == MODE_FWD_SUB || MODE == MODE_FWD_SUB_ADD) {
             // (x - NTT(y)) s mod q without canonicalising NTT(y) first: v < 12q
             // (round 3 ends with a CS stage), so d = x + 12q - v is in (0, 13q)
             // < 2^64, the lazy Shoup takes any 64-bit input to [0, 4q), and one
@@ -743,6 +746,14 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             const u64 q12 = M.q8 + M.q4;
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = canon4m(shoup_lazy(xx[k] + q12 - v[k], sc, scp, M), M);
+            if (MODE == MODE_FWD_SUB_ADD) {
+                // + add (ModAddFastEq on canonical operands), staged in as x was and
+                // into x's registers.  add may be dst itself: this thread reads the
+                // words it writes, and reads them first.
+                wave_stage_in<TEAM>(add + off + wq, lds, tid, xx);
+#pragma unroll
+                for (int k = 0; k < 16; k++) v[k] = csub(xx[k] + v[k], q);
+            }
             wave_stage_out<TEAM>(v, lds, tid, oblk + wq, live);
             return;
         }
@@ -940,6 +951,18 @@ __global__ __launch_bounds__(256, QP == 2 ? 3 : OFHE_KB_WAVES) void k_block(Plan
         block_body_q2<SPQ>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
     else
         block_body<MODE, SPQ, NR, SK>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
+}
+
+// k_block<MODE_FWD_SUB, ..> with an addend (MODE_FWD_SUB_ADD): a kernel of its
+// own, so that neither PlanArgs nor k_block's parameter list carries the pointer
+template <bool SPQ, int NR, int SK = 0>
+__global__ __launch_bounds__(256, OFHE_KB_WAVES) void k_block_add(PlanArgs P, const u64* src, u64* dst,
+                                                                  const u64* __restrict__ bdat, const u64* add,
+                                                                  u32 batch, u32 nwg) {
+    OFHE_VGPR_FLOOR();
+    __shared__ u64 lds[LDS_WORDS];
+    block_body<MODE_FWD_SUB_ADD, SPQ, NR, SK>(P, src, dst, bdat, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x,
+                                              add);
 }
 
 // Rescaling source of the forward column pass (k_cols / k_tcols <.., SWS = true>):

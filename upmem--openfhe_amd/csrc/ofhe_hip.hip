@@ -604,6 +604,18 @@ static void launch_block(const PlanArgs& a, bool spq, const u64* src, u64* dst, 
     }); });
 }
 
+// k_block_add: launch_block<MODE_FWD_SUB> with an addend laid out as dst
+static void launch_block_add(const PlanArgs& a, bool spq, const u64* src, u64* dst, const u64* b, const u64* add,
+                             u32 batch, hipStream_t s, int split) {
+    with_bool(spq, [&](auto sp) { with_int<8, 9, 12>((int)block_stages(split, a.log_n), [&](auto st) {
+        constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
+        const u32 nwg = NR == 2 ? ((batch + 3) / 4) * a.towers * (1u << (a.log_n - 10))
+                                : batch * a.towers * (1u << (a.log_n - 12));
+        hipLaunchKernelGGL((k_block_add<decltype(sp)::value, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b, add,
+                           batch, nwg);
+    }); });
+}
+
 template <int MODE>
 static void launch_small(const PlanArgs& a, bool spq, const u64* src, u64* dst, const u64* b, u32 batch,
                          hipStream_t s) {
@@ -691,7 +703,7 @@ int plan_ntt_inv_block(ofhe_plan_t p, u32 t0, u32 count, const u64* src, u64 sst
 }
 
 int plan_ntt_fwd_sub(ofhe_plan_t p, u32 t0, u32 count, u64* y, u64 ystride, const u64* x, u64 xstride, u64* out,
-                     u64 ostride, const u64* scal, u32 batch, hipStream_t s, int parts) {
+                     u64 ostride, const u64* scal, u32 batch, hipStream_t s, int parts, const u64* add) {
     if (!p || !p->ctx) return fail(OFHE_ERR_STATE, "plan is NULL or destroyed");
     if (p->log_n < 12) return fail(OFHE_ERR_ARG, "fused forward + subtract needs log_n >= 12");
     if (count == 0 || batch == 0) return OFHE_OK;
@@ -706,7 +718,10 @@ int plan_ntt_fwd_sub(ofhe_plan_t p, u32 t0, u32 count, u64* y, u64 ystride, cons
     ab.dstride = ostride;
     ab.bstride = xstride;
     ab.scal = scal;
-    launch_block<MODE_FWD_SUB>(ab, p->spq, y, out, x, batch, s, p->split);
+    if (add)
+        launch_block_add(ab, p->spq, y, out, x, add, batch, s, p->split);
+    else
+        launch_block<MODE_FWD_SUB>(ab, p->spq, y, out, x, batch, s, p->split);
     return post_launch();
 }
 }  // namespace ofhe
@@ -822,20 +837,31 @@ static int eltwise(ofhe_plan_t p, const u64* a, const u64* b, u64* c, u32 batch,
     return post_launch();
 }
 
+namespace ofhe {
+int tensor2_run(ofhe_plan_t p, u32 towers, const u64* c0, const u64* c1, const u64* d0, const u64* d1, u64* out0,
+                u64* out1, u64* out2, u32 batch, hipStream_t s) {
+    HIPCHK(hipSetDevice(p->ctx->device));
+    const u64 N = 1ull << p->log_n;
+    const u32 bpr = (u32)((N / 2 + 255) / 256);
+    const u64 blocks = (u64)bpr * batch * towers;
+    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large for one launch");
+    if (d0)
+        hipLaunchKernelGGL(k_tensor2<0>, dim3((u32)blocks), dim3(256), 0, s, p->d_tc, c0, c1, d0, d1, out0, out1, out2,
+                           bpr, p->log_n, towers);
+    else
+        hipLaunchKernelGGL(k_square2<0>, dim3((u32)blocks), dim3(256), 0, s, p->d_tc, c0, c1, out0, out1, out2, bpr,
+                           p->log_n, towers);
+    return post_launch();
+}
+}  // namespace ofhe
+
 int ofhe_hip_eval_mult_core(ofhe_plan_t p, const uint64_t* c0, const uint64_t* c1, const uint64_t* d0,
                             const uint64_t* d1, uint64_t* out0, uint64_t* out1, uint64_t* out2, uint32_t batch,
                             void* stream) {
     int rc = check_common(p, batch);
     if (rc) return rc;
     if (!c0 || !c1 || !d0 || !d1 || !out0 || !out1 || !out2) return fail(OFHE_ERR_ARG, "NULL data pointer");
-    HIPCHK(hipSetDevice(p->ctx->device));
-    const u64 N = 1ull << p->log_n;
-    const u32 bpr = (u32)((N / 2 + 255) / 256);
-    const u64 blocks = (u64)bpr * batch * p->towers;
-    if (blocks >= (1ull << 31)) return fail(OFHE_ERR_ARG, "batch too large for one launch");
-    hipLaunchKernelGGL(k_tensor2<0>, dim3((u32)blocks), dim3(256), 0, pick(stream), p->d_tc, c0, c1, d0, d1, out0,
-                       out1, out2, bpr, p->log_n, p->towers);
-    return post_launch();
+    return tensor2_run(p, p->towers, c0, c1, d0, d1, out0, out1, out2, batch, pick(stream));
 }
 
 int ofhe_hip_modmul_vv(ofhe_plan_t p, const uint64_t* a, const uint64_t* b, uint64_t* c, uint32_t batch,

@@ -1194,6 +1194,71 @@ public:
         return {std::move(o0), std::move(o1)};
     }
 
+    // one relinearisation key: the b and a polynomials, as KeySwitchCore takes them
+    typedef std::pair<const DCRTPolyHip*, const DCRTPolyHip*> RelinKey;
+
+    // LeveledSHEBase::EvalMult(ct1, ct2, evalKey) (base-leveledshe.cpp:199-218)
+    // followed by `levels` rescalings (ModReduceInternalInPlace:
+    // ckksrns-leveledshe.cpp:107-132 for OFHE_SHE_CKKS, t = 0;
+    // bgvrns-leveledshe.cpp:45-77 for OFHE_SHE_BGV with plaintext modulus t).
+    // The result is over the first Towers() - levels moduli of the operands.
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalMult(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
+                                                 const DCRTPolyHip& d1, const DCRTPolyHip& key_b,
+                                                 const DCRTPolyHip& key_a, int scheme = OFHE_SHE_CKKS, uint64_t t = 0,
+                                                 uint32_t levels = 0) const {
+        return mult("EvalMult", c0, c1, &d0, &d1, key_b, key_a, scheme, t, levels);
+    }
+    // LeveledSHEBase::EvalSquare(ct, evalKey) (base-leveledshe.cpp:262-280), then `levels` rescalings
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalSquare(const DCRTPolyHip& c0, const DCRTPolyHip& c1,
+                                                   const DCRTPolyHip& key_b, const DCRTPolyHip& key_a,
+                                                   int scheme = OFHE_SHE_CKKS, uint64_t t = 0,
+                                                   uint32_t levels = 0) const {
+        return mult("EvalSquare", c0, c1, nullptr, nullptr, key_b, key_a, scheme, t, levels);
+    }
+    // LeveledSHEBase::Relinearize (base-leveledshe.cpp:350-372): cv has 3 or
+    // more elements, keys[j - 2] = (b, a) switches element j
+    std::pair<DCRTPolyHip, DCRTPolyHip> Relinearize(const std::vector<const DCRTPolyHip*>& cv,
+                                                    const std::vector<RelinKey>& keys, uint64_t t = 0) const {
+        if (cv.size() < 3) throw math_error("Relinearize: 3 or more ciphertext elements expected");
+        if (keys.size() + 2 != cv.size()) throw math_error("Relinearize: one evaluation key per element past the second");
+        const uint32_t l = she_level("Relinearize", cv);
+        std::vector<const uint64_t*> c, kb, ka;
+        for (const DCRTPolyHip* e : cv) c.push_back(e->data());
+        for (const RelinKey& k : keys) {
+            check_key("Relinearize", *k.first, *k.second);
+            kb.push_back(k.first->data());
+            ka.push_back(k.second->data());
+        }
+        const DCRTPolyHip& f = *cv[0];
+        DCRTPolyHip o0(f.GetParams(), Format::EVALUATION, f.Batch(), DCRTPolyHip::Uninit{}),
+            o1(f.GetParams(), Format::EVALUATION, f.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_ks_relinearize(h_, l, (uint32_t)cv.size(), c.data(), kb.data(), ka.data(), o0.data(), o1.data(),
+                                      t, f.Batch(), nullptr),
+              "Relinearize");
+        return {std::move(o0), std::move(o1)};
+    }
+    // ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77) of every
+    // element of cv: `levels` >= 1 towers dropped, the results over the lowered params
+    std::vector<DCRTPolyHip> Rescale(const std::vector<const DCRTPolyHip*>& cv, int scheme = OFHE_SHE_CKKS,
+                                     uint64_t t = 0, uint32_t levels = 1) const {
+        if (cv.empty()) throw math_error("Rescale: one or more ciphertext elements expected");
+        const uint32_t l = she_level("Rescale", cv);
+        if (levels < 1 || levels >= l) throw math_error("Rescale: levels must be in [1, towers - 1]");
+        auto lp = lowered(*cv[0]->GetParams(), levels);
+        std::vector<DCRTPolyHip> out;
+        std::vector<const uint64_t*> x;
+        std::vector<uint64_t*> o;
+        for (const DCRTPolyHip* e : cv) {
+            out.emplace_back(lp, Format::EVALUATION, e->Batch(), DCRTPolyHip::Uninit{});
+            x.push_back(e->data());
+        }
+        for (DCRTPolyHip& r : out) o.push_back(r.data());
+        check(ofhe_hip_ks_rescale(h_, l, scheme, t, levels, (uint32_t)cv.size(), x.data(), o.data(), cv[0]->Batch(),
+                                  nullptr),
+              "Rescale");
+        return out;
+    }
+
     // The digits of one ciphertext's c1 (EvalKeySwitchPrecomputeCore), kept on
     // the device for any number of hoisted rotations.
     struct HoistedDigits {
@@ -1355,6 +1420,49 @@ private:
     struct KeyPtrs {
         std::vector<const uint64_t*> b, a;
     };
+    // the checks KeySwitchCore makes, for the multiplication family
+    void check_key(const char* op, const DCRTPolyHip& key_b, const DCRTPolyHip& key_a) const {
+        if (key_b.Batch() != numPartQ_ || key_a.Batch() != numPartQ_ ||
+            key_b.GetParams()->Towers() != sizeQ_ + sizeP_ || key_a.GetParams()->Towers() != sizeQ_ + sizeP_)
+            throw math_error(std::string(op) + ": evaluation key must be numPartQ polynomials over Q|P");
+    }
+    // every element in EVALUATION form, over one basis of at most Q's towers, of one batch: the level
+    uint32_t she_level(const char* op, const std::vector<const DCRTPolyHip*>& cv) const {
+        const std::string w(op);
+        for (const DCRTPolyHip* e : cv) {
+            if (!e) throw math_error(w + ": NULL ciphertext element");
+            if (e->GetFormat() != Format::EVALUATION) throw math_error(w + ": EVALUATION form expected");
+            if (e->GetParams()->Moduli() != cv[0]->GetParams()->Moduli() || e->Batch() != cv[0]->Batch())
+                throw math_error(w + ": elements over one basis and of one batch expected");
+        }
+        const size_t l = cv[0]->GetParams()->Towers();
+        if (l > sizeQ_) throw math_error(w + ": ciphertext has more towers than Q");
+        return (uint32_t)l;
+    }
+    // DropLastElement `levels` times (dcrtpoly-impl.h:719-728): the params of the shorter chain
+    static std::shared_ptr<DCRTParams> lowered(const DCRTParams& p, uint32_t levels) {
+        if (levels >= p.Towers()) throw math_error("Removing last element of DCRTPoly object renders it invalid!");
+        std::vector<uint64_t> q(p.Moduli().begin(), p.Moduli().end() - levels);
+        std::vector<uint64_t> r(p.Roots().begin(), p.Roots().end() - levels);
+        return std::make_shared<DCRTParams>(p.GetCyclotomicOrder(), q, r, p.manager()->device());
+    }
+    std::pair<DCRTPolyHip, DCRTPolyHip> mult(const char* op, const DCRTPolyHip& c0, const DCRTPolyHip& c1,
+                                             const DCRTPolyHip* d0, const DCRTPolyHip* d1, const DCRTPolyHip& key_b,
+                                             const DCRTPolyHip& key_a, int scheme, uint64_t t, uint32_t levels) const {
+        std::vector<const DCRTPolyHip*> cv{&c0, &c1};
+        if (d0) cv.insert(cv.end(), {d0, d1});
+        const uint32_t l = she_level(op, cv);
+        check_key(op, key_b, key_a);
+        if (levels >= l) throw math_error(std::string(op) + ": levels must be below the towers of the operands");
+        auto lp = levels ? lowered(*c0.GetParams(), levels) : c0.GetParams();
+        DCRTPolyHip o0(lp, Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{}),
+            o1(lp, Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{});
+        check(ofhe_hip_ks_eval_mult(h_, l, c0.data(), c1.data(), d0 ? d0->data() : nullptr, d1 ? d1->data() : nullptr,
+                                    key_b.data(), key_a.data(), scheme, t, levels, o0.data(), o1.data(), c0.Batch(),
+                                    nullptr),
+              op);
+        return {std::move(o0), std::move(o1)};
+    }
     void rot_check(const char* op, const DCRTPolyHip* c0, const HoistedDigits& digits,
                    const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys) const {
         const std::string w(op);

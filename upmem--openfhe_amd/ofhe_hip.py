@@ -34,6 +34,9 @@ Host-side mirror of the reference's offload interface for the hot path:
   (rns-pke.cpp:199-224), the two ``ScaleAndRound`` overloads to a ``NativePoly`` mod t
   (dcrtpoly-impl.h:1537-1814, 2005-2049), the one-tower ``MultiplyAndRound`` path, and
   ``DCRTPolyImpl::TimesQovert`` (dcrtpoly-impl.h:1015-1031); its tables are a ``bfv_tables.DecryptTables``.
+* ``KeySwitch.eval_mult`` / ``eval_square`` / ``relinearize`` / ``rescale`` ~ ``LeveledSHEBase::EvalMult`` /
+  ``EvalSquare`` with an evaluation key and ``RelinearizeInPlace`` (base-leveledshe.cpp:199-372) and
+  ``ModReduceInternalInPlace`` of CKKS and BGV (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77).
 * ``switch_modulus`` / ``NTTPlan.automorphism`` ~ ``NativeVectorT::SwitchModulus``
   (mubintvecnat.cpp:111-136) / ``PolyImpl::AutomorphismTransform`` (poly-impl.h:312-365).
 
@@ -55,6 +58,10 @@ LIB_PATH = os.path.join(_HERE, "lib", "libofhe_hip.so")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
+
+
+# scheme of KeySwitch.eval_mult / rescale (OFHE_SHE_*)
+SHE_CKKS, SHE_BGV = 0, 1
 
 
 class MathError(RuntimeError):
@@ -160,6 +167,14 @@ _SIGS = {
                                                          ctypes.c_uint32, _vp]),
     "ofhe_hip_ks_bsgs_transform": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(Bsgs), _vp, _vp, _vp, _vp,
                                                   ctypes.c_uint64, ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_rescale": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_uint32,
+                                           _vp]),
+    "ofhe_hip_ks_relinearize": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp),
+                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, ctypes.c_uint64,
+                                               ctypes.c_uint32, _vp]),
+    "ofhe_hip_ks_eval_mult": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                             ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_switch_modulus": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                _vp]),
     "ofhe_hip_automorphism": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
@@ -1017,6 +1032,50 @@ class KeySwitch:
         _check(lib().ofhe_hip_ks_bsgs_transform(self._h, int(size_ql), ctypes.byref(tr), _vp(c0 or None),
                                                 _vp(c1 or None), _vp(out0 or None), _vp(out1 or None), int(t),
                                                 int(batch), _vp(stream or None)))
+
+    @staticmethod
+    def _ptrs(v):
+        """Host array of device pointers; None stays NULL, a 0 entry a NULL entry."""
+        return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
+
+    def eval_mult(self, size_ql: int, c0: int, c1: int, d0: int, d1: int, key_b: int, key_a: int, out0: int,
+                  out1: int, scheme: int = SHE_CKKS, t: int = 0, levels: int = 0, batch: int = 1,
+                  stream: int = 0) -> None:
+        """LeveledSHEBase::EvalMult(ct1, ct2, evalKey) (base-leveledshe.cpp:199-259) followed by ``levels``
+        rescalings (ModReduceInternalInPlace of the scheme); d0 = d1 = 0: EvalSquare.  out0, out1:
+        [batch][size_ql - levels][N]."""
+        _check(lib().ofhe_hip_ks_eval_mult(self._h, int(size_ql), _vp(c0 or None), _vp(c1 or None), _vp(d0 or None),
+                                           _vp(d1 or None), _vp(key_b or None), _vp(key_a or None), int(scheme),
+                                           int(t), int(levels), _vp(out0 or None), _vp(out1 or None), int(batch),
+                                           _vp(stream or None)))
+
+    def eval_square(self, size_ql: int, c0: int, c1: int, key_b: int, key_a: int, out0: int, out1: int,
+                    scheme: int = SHE_CKKS, t: int = 0, levels: int = 0, batch: int = 1, stream: int = 0) -> None:
+        """LeveledSHEBase::EvalSquare(ct, evalKey) (base-leveledshe.cpp:262-319), then ``levels`` rescalings."""
+        self.eval_mult(size_ql, c0, c1, 0, 0, key_b, key_a, out0, out1, scheme, t, levels, batch, stream)
+
+    def relinearize(self, size_ql: int, elements: Sequence[int], key_b_ptrs: Sequence[int],
+                    key_a_ptrs: Sequence[int], out0: int, out1: int, t: int = 0, batch: int = 1,
+                    stream: int = 0) -> None:
+        """LeveledSHEBase::RelinearizeInPlace (base-leveledshe.cpp:357-372) of len(elements) >= 3 elements
+        under len(elements) - 2 keys; out0 may be elements[0], out1 elements[1]."""
+        n = 0 if elements is None else len(elements)
+        for v in (key_b_ptrs, key_a_ptrs):
+            if v is not None and elements is not None and n >= 2 and len(v) != n - 2:
+                raise MathError("one evaluation key per element past the second required")
+        _check(lib().ofhe_hip_ks_relinearize(self._h, int(size_ql), n, self._ptrs(elements), self._ptrs(key_b_ptrs),
+                                             self._ptrs(key_a_ptrs), _vp(out0 or None), _vp(out1 or None), int(t),
+                                             int(batch), _vp(stream or None)))
+
+    def rescale(self, size_ql: int, x_ptrs: Sequence[int], out_ptrs: Sequence[int], scheme: int = SHE_CKKS,
+                t: int = 0, levels: int = 1, batch: int = 1, stream: int = 0) -> None:
+        """ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77): ``levels``
+        rescalings of every element; out_ptrs[k]: [batch][size_ql - levels][N]."""
+        if x_ptrs is not None and out_ptrs is not None and len(x_ptrs) != len(out_ptrs):
+            raise MathError("one output per element required")
+        n = 0 if x_ptrs is None else len(x_ptrs)
+        _check(lib().ofhe_hip_ks_rescale(self._h, int(size_ql), int(scheme), int(t), int(levels), n,
+                                         self._ptrs(x_ptrs), self._ptrs(out_ptrs), int(batch), _vp(stream or None)))
 
 
 def comm_unique_id() -> bytes:
