@@ -416,6 +416,7 @@ def test_argument_errors(hip):
         dict(batch=0),
         dict(diag_stride=(l + sp) * n - 1),
         dict(out1=o0.data_ptr()),                                                  # out0 == out1
+        dict(out1=o0.data_ptr() + 8),                                              # out1 one word into out0
         dict(out0=bs.d_c0.data_ptr()), dict(out1=bs.d_c1.data_ptr()),              # outputs aliasing inputs
         dict(out0=bs.d_diag.data_ptr()),
     ]
@@ -435,7 +436,8 @@ def test_argument_errors(hip):
                 stream=stream())
     for over in (dict(x0=0), dict(x1=0), dict(diag=0), dict(out0=0), dict(out1=0), dict(nterm=0), dict(nsum=0),
                  dict(batch=0), dict(diag_stride=poly - 1), dict(x_stride=per - 1), dict(out1=e0.data_ptr()),
-                 dict(out0=d0.data_ptr()), dict(out1=dd.data_ptr()), dict(size_ql=sq + 1)):
+                 dict(out1=e0.data_ptr() + 8), dict(out0=d0.data_ptr()), dict(out1=dd.data_ptr()),
+                 dict(size_ql=sq + 1)):
         with pytest.raises(H.MathError):
             ks.mult_ext_sum(**{**good, **over})
     f0, f1 = zeros(B, l + sp, n), zeros(B, l + sp, n)
@@ -445,7 +447,7 @@ def test_argument_errors(hip):
     for over in (dict(digits=0), dict(out0=0), dict(out1=0), dict(auto_indices=None), dict(key_b_ptrs=None),
                  dict(key_a_ptrs=None), dict(auto_indices=[5, 4]), dict(key_b_ptrs=[0, 0]), dict(batch=0),
                  dict(auto_indices=[], key_b_ptrs=[], key_a_ptrs=[]), dict(out1=f0.data_ptr()),
-                 dict(out0=dg.data_ptr()), dict(nadd=1), dict(addend1=e0.data_ptr())):
+                 dict(out1=f0.data_ptr() + 8), dict(out0=dg.data_ptr()), dict(nadd=1), dict(addend1=e0.data_ptr())):
         with pytest.raises(H.MathError):
             ks.fast_rotation_ext_sum(**{**good, **over})
     for c, out, batch in ((0, f0.data_ptr(), B), (bs.d_c0.data_ptr(), 0, B), (bs.d_c0.data_ptr(), f0.data_ptr(), 0),

@@ -48,6 +48,14 @@ TowerScalar scalar_of(u64 q, u64 s) {
     return TowerScalar{q, s, shoup_pre(s, q)};
 }
 
+// ApproxModDown's plaintext-modulus tables: [P] t^-1 mod p_j (tInvModp), then [Q] t mod q_i
+std::vector<TowerScalar> t_tables(const u64* p, u32 P, const u64* q, u32 Q, u64 t) {
+    std::vector<TowerScalar> tab(P + Q);
+    for (u32 j = 0; j < P; j++) tab[j] = scalar_of(p[j], invmod(t % p[j], p[j]));
+    for (u32 i = 0; i < Q; i++) tab[P + i] = scalar_of(q[i], t);
+    return tab;
+}
+
 int scale_towers(const TowerScalar* d, const u64* x, u64* out, u64 xs, u64 os, u32 batch, u32 towers, u32 log_n,
                  hipStream_t s) {
     const u64 npairs = ((u64)batch * towers << log_n) / 2;
@@ -195,11 +203,11 @@ int ofhe_hip_approx_mod_down(ofhe_plan_t pq, ofhe_plan_t pp, ofhe_bconv_t bc, co
     key.push_back(t);
     const u64* dtab = nullptr;
     RCCHK(cached_table(bc->tab_mu, bc->tabs, key, "mod-down tables", &dtab, [&] {
-        std::vector<TowerScalar> tab(Q + (t ? P + Q : 0));
+        std::vector<TowerScalar> tab(Q);
         for (u32 i = 0; i < Q; i++) tab[i] = scalar_of(pq->q[i], p_inv_modq[i]);
         if (t) {
-            for (u32 j = 0; j < P; j++) tab[Q + j] = scalar_of(pp->q[j], invmod(t % pp->q[j], pp->q[j]));  // tInvModp
-            for (u32 i = 0; i < Q; i++) tab[Q + P + i] = scalar_of(pq->q[i], t);  // t mod q_i
+            const auto tt = t_tables(pp->q.data(), P, pq->q.data(), Q, t);
+            tab.insert(tab.end(), tt.begin(), tt.end());
         }
         return tab;
     }));
@@ -223,7 +231,10 @@ struct KsLevel {
     std::map<u64, TowerScalar*> tscale; // t -> [size_p] t^-1 mod p_j, then [size_ql] t mod q_i
 };
 
+// One rescaling step's host tables (rs_build): the k_switch_scale mode, its sw rows, the sc rows of
+// the forward-subtract pass (evaluation form) and the scalar applied to the last tower before the lift
 struct RsTab {
+    int mode = 0;
     std::vector<u64> sw, sc;
     u64 pre = 1;
 };
@@ -242,6 +253,10 @@ struct ofhe_ks_s {
     // rescaling tables for dropping tower `towers - 1`, keyed by (towers, t) with t = 0 for CKKS:
     // rescale_run's sw / sc words and ModReduce's negtInvModq (rs_tables)
     std::map<std::pair<u32, u64>, RsTab> rescale;
+    // words of a polynomial over Ql (l towers), of one over Ql|P, and of one digit of an evaluation key
+    u64 words_q(u32 l) const { return (u64)l << log_n; }
+    u64 words_qp(u32 l) const { return (u64)(l + size_p) << log_n; }
+    u64 key_stride() const { return words_qp(size_q); }
 };
 
 static void level_free(KsLevel* L) {
@@ -422,13 +437,8 @@ static int level_get(ofhe_ks_t k, u32 size_ql, KsLevel** out) {
 }
 
 static int level_t_tables(ofhe_ks_t k, KsLevel* L, u64 t, const TowerScalar** out) {
-    return cached_table(k->mu, L->tscale, t, "t tables", out, [&] {
-        const u32 P = k->size_p, l = L->size_ql;
-        std::vector<TowerScalar> tab(P + l);
-        for (u32 j = 0; j < P; j++) tab[j] = scalar_of(k->p[j], invmod(t % k->p[j], k->p[j]));
-        for (u32 i = 0; i < l; i++) tab[P + i] = scalar_of(k->q[i], t);
-        return tab;
-    });
+    return cached_table(k->mu, L->tscale, t, "t tables", out,
+                        [&] { return t_tables(k->p.data(), k->size_p, k->q.data(), L->size_ql, t); });
 }
 
 // The key-switch engine's ApproxModDown (P -> the level's Q towers) with
@@ -487,13 +497,19 @@ static int ks_check(ofhe_ks_t k, u32 size_ql, u32 batch) {
     return OFHE_OK;
 }
 
+// The prologue of an entry point that works at one level: the engine checks, then that level's tables
+static int ks_enter(ofhe_ks_t k, u32 size_ql, u32 batch, KsLevel** L) {
+    RCCHK(ks_check(k, size_ql, batch));
+    return level_get(k, size_ql, L);
+}
+
 // EvalKeySwitchPrecomputeCore; with own_copy = false the digit's own towers
 // are left out of its slot (KeySwitchCore's inner product reads them from c).
 static int ks_precompute_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, const uint64_t* c, uint64_t* digits,
                               uint32_t batch, hipStream_t stream, bool own_copy) {
     KsFork fk;
     RCCHK(fk.open(k, stream));
-    const u64 N = 1ull << k->log_n, l = size_ql, P = k->size_p, poly = (l + P) * N, ds = L->beta * poly;
+    const u64 N = 1ull << k->log_n, l = size_ql, P = k->size_p, poly = k->words_qp(l), ds = L->beta * poly;
     // ModUp in chunks of ciphertexts (OFHE_KS_CHUNK), so that a chunk's
     // converted towers can still sit in the Infinity Cache when its forward
     // transform reads them
@@ -548,10 +564,9 @@ static int ks_precompute_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, const u
 
 int ofhe_hip_ks_precompute(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, uint64_t* digits, uint32_t batch,
                            void* stream) {
-    RCCHK(ks_check(k, size_ql, batch));
-    if (!c || !digits) return fail(OFHE_ERR_ARG, "NULL data pointer");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    if (!c || !digits) return fail(OFHE_ERR_ARG, "NULL data pointer");
     return ks_precompute_impl(k, L, size_ql, c, digits, batch, pick(stream), true);
 }
 
@@ -561,18 +576,19 @@ static int ks_fast_core_ext_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, cons
                                  const uint64_t* key_b, const uint64_t* key_a, uint64_t* ct0, uint64_t* ct1,
                                  uint32_t batch, void* stream, const uint64_t* c) {
     const u32 towers = size_ql + k->size_p;
-    const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
+    const u64 key_stride = k->key_stride();
     if (L->beta <= 4) {
         // batch-stationary keys: one thread per (tower, OFHE_KS_CPT coefficients)
-        const u64 rows = ((u64)towers << k->log_n) / OFHE_KS_CPT;
-        const dim3 g((u32)((rows + 255) / 256)), blk(256);
+        const u64 rows = k->words_qp(size_ql) / OFHE_KS_CPT;
+        dim3 g, blk(256);
+        RCCHK(coeff_grid(rows, &g));
         hipStream_t s = pick(stream);
         KsOwn own{};
         for (u32 j = 0; j < L->beta; j++) {
             own.start[j] = L->start[j];
             own.cnt[j] = L->cnt[j];
         }
-        const u64 c_stride = (u64)size_ql << k->log_n;
+        const u64 c_stride = k->words_q(size_ql);
         // beta is in [1, 4] here (ofhe_hip_ks_digits); anything else took the beta = 4 kernel before too
         with_int<1, 2, 3, 4>(L->beta ? (int)L->beta : 4, [&](auto B_) {
             hipLaunchKernelGGL((k_ks_inner_bs<decltype(B_)::value, OFHE_KS_CPT>), g, blk, 0, s, L->d_tow, digits, key_b,
@@ -580,7 +596,7 @@ static int ks_fast_core_ext_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, cons
         });
     } else {
         if (c) return fail(OFHE_ERR_STATE, "internal: own-tower reads need beta <= 4");
-        const u64 npairs = ((u64)batch * towers << k->log_n) / 2;
+        const u64 npairs = batch * k->words_qp(size_ql) / 2;
         hipLaunchKernelGGL(k_ks_inner, dim3(grid_for(npairs)), dim3(256), 0, pick(stream), L->d_tow, digits, key_b,
                            key_a, ct0, ct1, key_stride, L->beta, npairs, k->log_n, towers);
     }
@@ -589,33 +605,30 @@ static int ks_fast_core_ext_impl(ofhe_ks_t k, KsLevel* L, uint32_t size_ql, cons
 
 int ofhe_hip_ks_fast_core_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t* digits, const uint64_t* key_b,
                               const uint64_t* key_a, uint64_t* ct0, uint64_t* ct1, uint32_t batch, void* stream) {
-    RCCHK(ks_check(k, size_ql, batch));
-    if (!digits || !key_b || !key_a || !ct0 || !ct1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    if (!digits || !key_b || !key_a || !ct0 || !ct1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     return ks_fast_core_ext_impl(k, L, size_ql, digits, key_b, key_a, ct0, ct1, batch, stream, nullptr);
 }
 
 static int ks_mod_down_impl(ofhe_ks_t k, KsLevel* L, const u64* x, u64* out, u64 t, u32 batch, hipStream_t s) {
     ModDownArgs A;
     RCCHK(ks_md_args(k, L, t, &A));
-    const u64 N = 1ull << k->log_n, l = L->size_ql;
-    return mod_down_run(A, x, (l + k->size_p) * N, &out, 1, l * N, batch, s);
+    return mod_down_run(A, x, k->words_qp(L->size_ql), &out, 1, k->words_q(L->size_ql), batch, s);
 }
 
 int ofhe_hip_ks_mod_down(ofhe_ks_t k, uint32_t size_ql, const uint64_t* x, uint64_t* out, uint64_t t, uint32_t batch,
                          void* stream) {
-    RCCHK(ks_check(k, size_ql, batch));
-    if (!x || !out) return fail(OFHE_ERR_ARG, "NULL data pointer");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    if (!x || !out) return fail(OFHE_ERR_ARG, "NULL data pointer");
     return ks_mod_down_impl(k, L, x, out, t, batch, pick(stream));
 }
 
 // KeySwitchCore of c into out0 / out1, plus add0 / add1 when given (mod_down_run)
 static int ks_core_impl(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* c, const u64* key_b, const u64* key_a,
                         u64* out0, u64* out1, const u64* add0, const u64* add1, u64 t, u32 batch, hipStream_t s) {
-    const u64 N = 1ull << k->log_n, poly = (u64)(size_ql + k->size_p) * N;
+    const u64 poly = k->words_qp(size_ql);
     Scratch dg, ct;
     RCCHK(dg.alloc((size_t)batch * L->beta * poly * 8, s, k->ctx));
     RCCHK(ct.alloc((size_t)2 * batch * poly * 8, s, k->ctx));
@@ -631,15 +644,14 @@ static int ks_core_impl(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* c, cons
     RCCHK(ks_md_args(k, L, t, &A));
     u64* const outs[2] = {out0, out1};
     const u64* const adds[2] = {add0, add1};
-    return mod_down_run(A, c0, poly, outs, 2, (u64)size_ql * N, batch, s, add0 ? adds : nullptr);
+    return mod_down_run(A, c0, poly, outs, 2, k->words_q(size_ql), batch, s, add0 ? adds : nullptr);
 }
 
 int ofhe_hip_ks_core(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, const uint64_t* key_b, const uint64_t* key_a,
                      uint64_t* out0, uint64_t* out1, uint64_t t, uint32_t batch, void* stream) {
-    RCCHK(ks_check(k, size_ql, batch));
-    if (!c || !key_b || !key_a || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    if (!c || !key_b || !key_a || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     return ks_core_impl(k, L, size_ql, c, key_b, key_a, out0, out1, nullptr, nullptr, t, batch, pick(stream));
 }
 
@@ -653,21 +665,45 @@ static u32 inv_odd32(u32 k) {
     return x;
 }
 
-// Argument checks shared by the two calls; kinv[r] = auto_index[r]^-1.
+// an index that is 1 modulo 2N (id_mask = 2N - 1) is the identity: no rotation, no key read
+static bool rot_is_id(u32 index, u32 id_mask) { return (index & id_mask) == 1; }
+
+// The rules of a list of n rotations: every key given, every index odd.
+// key_b = NULL checks the indices alone (the BSGS call tests them before it has
+// an engine); id_mask = 2N - 1 lets identity steps go without keys (BSGS again),
+// 0 exempts none.
+static int rot_list_check(u32 n, const u32* index, const u64* const* key_b, const u64* const* key_a,
+                          u32 id_mask = 0) {
+    for (u32 r = 0; r < n; r++) {
+        if (key_b && !rot_is_id(index[r], id_mask) && (!key_b[r] || !key_a[r]))
+            return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
+        if (index[r] % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
+    }
+    return OFHE_OK;
+}
+
+// Argument checks shared by the two calls, and their level; kinv[r] = auto_index[r]^-1.
 static int rot_check(ofhe_ks_t k, u32 size_ql, const u64* digits, u32 nrot, const u32* auto_index,
                      const u64* const* key_b, const u64* const* key_a, const u64* out0, const u64* out1, u32 batch,
-                     std::vector<u32>& kinv) {
-    RCCHK(ks_check(k, size_ql, batch));
+                     std::vector<u32>& kinv, KsLevel** L) {
+    RCCHK(ks_enter(k, size_ql, batch, L));
     if (!digits || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     if (!auto_index || !key_b || !key_a) return fail(OFHE_ERR_ARG, "NULL index or key pointer array");
     if (nrot == 0) return fail(OFHE_ERR_ARG, "nrot must be >= 1");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    RCCHK(rot_list_check(nrot, auto_index, key_b, key_a));
     kinv.resize(nrot);
-    for (u32 r = 0; r < nrot; r++) {
-        if (!key_b[r] || !key_a[r]) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
-        if (auto_index[r] % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
-        kinv[r] = inv_odd32(auto_index[r]);
-    }
+    for (u32 r = 0; r < nrot; r++) kinv[r] = inv_odd32(auto_index[r]);
+    return OFHE_OK;
+}
+
+// f(j0, n) for the chunks [j0, j0 + n) of at most KS_ROT_CAP items, the most one
+// launch's arguments carry; or_once: one call f(0, 0) for an empty list, whose
+// launch still has other work to do
+template <class F>
+static int rot_chunks(u32 total, bool or_once, F&& f) {
+    if (!total && or_once) return f(0u, 0u);
+    for (u32 j0 = 0; j0 < total; j0 += KS_ROT_CAP) RCCHK(f(j0, std::min(KS_ROT_CAP, total - j0)));
     return OFHE_OK;
 }
 
@@ -682,9 +718,9 @@ static int ks_inner_rot(ofhe_ks_t k, KsLevel* L, u32 size_ql, const u64* digits,
         R.kinv[r] = kinv[r];
     }
     const u32 towers = size_ql + k->size_p;
-    const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
-    const u64 nthreads = (u64)batch * towers << k->log_n;
-    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
+    const u64 key_stride = k->key_stride(), nthreads = batch * k->words_qp(size_ql);
+    dim3 g, blk(256);
+    RCCHK(coeff_grid(nthreads, &g));
     const bool narrow = with_int<1, 2, 3, 4>((int)L->beta, [&](auto B_) {
         hipLaunchKernelGGL((k_ks_inner_rot<decltype(B_)::value>), g, blk, 0, s, L->d_tow, digits, c0, L->d_pmodq, R,
                            nrot, out0, out1, key_stride, rot_stride, nthreads, k->log_n, towers, size_ql);
@@ -700,15 +736,13 @@ int ofhe_hip_ks_fast_rotation_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t*
                                   const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint32_t batch,
                                   void* stream) {
     std::vector<u32> kinv;
-    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv));
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
-    const u64 rot_stride = (u64)batch * (size_ql + k->size_p) << k->log_n;
-    for (u32 r0 = 0; r0 < nrot; r0 += KS_ROT_CAP)
-        RCCHK(ks_inner_rot(k, L, size_ql, digits, c0, std::min(KS_ROT_CAP, nrot - r0), kinv.data() + r0, key_b + r0,
-                           key_a + r0, out0 + r0 * rot_stride, out1 + r0 * rot_stride, rot_stride, batch,
-                           pick(stream)));
-    return OFHE_OK;
+    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv, &L));
+    const u64 rot_stride = batch * k->words_qp(size_ql);
+    return rot_chunks(nrot, false, [&](u32 r0, u32 nr) {
+        return ks_inner_rot(k, L, size_ql, digits, c0, nr, kinv.data() + r0, key_b + r0, key_a + r0,
+                            out0 + r0 * rot_stride, out1 + r0 * rot_stride, rot_stride, batch, pick(stream));
+    });
 }
 
 int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* digits, const uint64_t* c0,
@@ -716,21 +750,19 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
                               const uint64_t* const* key_a, uint64_t* out0, uint64_t* out1, uint64_t t,
                               uint32_t batch, void* stream) {
     std::vector<u32> kinv;
-    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv));
-    if (!c0) return fail(OFHE_ERR_ARG, "NULL data pointer");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(rot_check(k, size_ql, digits, nrot, auto_index, key_b, key_a, out0, out1, batch, kinv, &L));
+    if (!c0) return fail(OFHE_ERR_ARG, "NULL data pointer");
     hipStream_t s = pick(stream);
     ModDownArgs A;
     RCCHK(ks_md_args(k, L, t, &A));
-    const u32 l = L->size_ql, P = k->size_p;
-    const u64 N = 1ull << k->log_n, poly = (u64)(l + P) * N, per_rot = (u64)batch * l * N;
+    const u32 l = L->size_ql;
+    const u64 poly = k->words_qp(l), per_rot = batch * k->words_q(l);
     u32 one[KS_ROT_CAP];
     for (auto& v : one) v = 1;
     // the order of the reference: ModDown, += c0, then the automorphism
     // (ModDown and the automorphism do not commute bit for bit)
-    for (u32 r0 = 0; r0 < nrot; r0 += KS_ROT_CAP) {
-        const u32 nr = std::min(KS_ROT_CAP, nrot - r0);
+    return rot_chunks(nrot, false, [&](u32 r0, u32 nr) -> int {
         Scratch ct, md;
         RCCHK(ct.alloc((size_t)2 * nr * batch * poly * 8, s, k->ctx));
         RCCHK(md.alloc((size_t)2 * nr * per_rot * 8, s, k->ctx));
@@ -741,14 +773,13 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
         RCCHK(ks_inner_rot(k, L, size_ql, digits, nullptr, nr, one, key_b + r0, key_a + r0, ct.w(), ct1,
                            (u64)batch * poly, batch, s));
         u64* const mds[2] = {md.w(), md1};
-        RCCHK(mod_down_run(A, ct.w(), poly, mds, 2, (u64)l * N, nr * batch, s));
+        RCCHK(mod_down_run(A, ct.w(), poly, mds, 2, k->words_q(l), nr * batch, s));
         KsRotIdx I{};
         for (u32 r = 0; r < nr; r++) I.kinv[r] = kinv[r0 + r];
         hipLaunchKernelGGL(k_add_automorphism, dim3(grid_for(per_rot), nr), dim3(256), 0, s, L->d_tow, md.w(), md1,
                            c0, out0 + r0 * per_rot, out1 + r0 * per_rot, I, per_rot, k->log_n, l);
-        RCCHK(post_launch());
-    }
-    return OFHE_OK;
+        return post_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -757,21 +788,21 @@ int ofhe_hip_ks_fast_rotation(ofhe_ks_t k, uint32_t size_ql, const uint64_t* dig
 // ---------------------------------------------------------------------------
 static int ks_ext_impl(ofhe_ks_t k, KsLevel* L, const u64* c, u64* out, u32 batch, hipStream_t s) {
     const u32 towers = L->size_ql + k->size_p;
-    const u64 nthreads = (u64)batch * towers << k->log_n;
-    hipLaunchKernelGGL(k_ks_ext, dim3((u32)((nthreads + 255) / 256)), dim3(256), 0, s, L->d_pmodq, c, out, nthreads,
-                       k->log_n, towers, L->size_ql);
+    const u64 nthreads = batch * k->words_qp(L->size_ql);
+    dim3 g;
+    RCCHK(coeff_grid(nthreads, &g));
+    hipLaunchKernelGGL(k_ks_ext, g, dim3(256), 0, s, L->d_pmodq, c, out, nthreads, k->log_n, towers, L->size_ql);
     return post_launch();
 }
 
 int ofhe_hip_ks_ext(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c, uint64_t* out, uint32_t batch, void* stream) {
     if (!c || !out) return fail(OFHE_ERR_ARG, "NULL data pointer");
+    // ahead of the engine's checks, which would report a missing engine first
     if (batch == 0) return fail(OFHE_ERR_ARG, "batch must be >= 1");
-    RCCHK(ks_check(k, size_ql, batch));
-    const u64 N = 1ull << k->log_n;
-    if (words_overlap(c, (u64)batch * size_ql * N, out, (u64)batch * (size_ql + k->size_p) * N))
-        return fail(OFHE_ERR_ARG, "out must not alias c");
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    if (words_overlap(c, batch * k->words_q(size_ql), out, batch * k->words_qp(size_ql)))
+        return fail(OFHE_ERR_ARG, "out must not alias c");
     return ks_ext_impl(k, L, c, out, batch, pick(stream));
 }
 
@@ -782,8 +813,9 @@ static int lt_inner_run(ofhe_ks_t k, KsLevel* L, u32 nterm, const u64* x0, const
                         const u64* diag, u64 diag_stride, const uint8_t* present, const u32* rows, u32 nsum,
                         u64* out0, u64* out1, u32 batch, hipStream_t s) {
     const u32 towers = L->size_ql + k->size_p;
-    const u64 nthreads = (u64)batch * towers << k->log_n;
-    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
+    const u64 nthreads = batch * k->words_qp(L->size_ql);
+    dim3 g, blk(256);
+    RCCHK(coeff_grid(nthreads, &g));
     for (u32 g0 = 0; g0 < nsum; g0 += LT_SUM_CAP) {
         const u32 ns = std::min(LT_SUM_CAP, nsum - g0);
         for (u32 i0 = 0; i0 < nterm; i0 += LT_TERM_CAP) {
@@ -808,6 +840,25 @@ static int lt_inner_run(ofhe_ks_t k, KsLevel* L, u32 nterm, const u64* x0, const
     return OFHE_OK;
 }
 
+// The aliasing policy of a pair of outputs of ow words each (that they are two
+// buffers, out0 != out1, is tested ahead of the engine): they do not overlap ...
+static int outputs_apart(const u64* out0, const u64* out1, u64 ow) {
+    if (words_overlap(out0, ow, out1, ow)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    return OFHE_OK;
+}
+// ... and, first, neither overlaps a span of input words (a NULL span is an absent input)
+struct WordSpan {
+    const u64* p;
+    u64 words;
+};
+static int outputs_check(const u64* out0, const u64* out1, u64 ow, std::initializer_list<WordSpan> inputs) {
+    for (const u64* o : {out0, out1})
+        for (const WordSpan& in : inputs)
+            if (in.p && words_overlap(o, ow, in.p, in.words))
+                return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
+    return outputs_apart(out0, out1, ow);
+}
+
 int ofhe_hip_ks_mult_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t nterm, const uint64_t* x0, const uint64_t* x1,
                              uint64_t x_stride, const uint64_t* diag, uint64_t diag_stride, const uint8_t* present,
                              uint32_t nsum, uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream) {
@@ -815,18 +866,14 @@ int ofhe_hip_ks_mult_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t nterm, cons
     if (!x0 || !x1 || !diag || !out0 || !out1) return fail(OFHE_ERR_ARG, "NULL data pointer");
     if (nterm == 0 || nsum == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nterm, nsum and batch must be >= 1");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
-    RCCHK(ks_check(k, size_ql, batch));
-    const u64 poly = (u64)(size_ql + k->size_p) << k->log_n, per = (u64)batch * poly;
+    KsLevel* L = nullptr;
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    const u64 poly = k->words_qp(size_ql), per = batch * poly;
     if (diag_stride < poly) return fail(OFHE_ERR_ARG, "diag_stride smaller than one diagonal");
     if (x_stride < per) return fail(OFHE_ERR_ARG, "x_stride smaller than one term");
-    const u64 xw = (u64)(nterm - 1) * x_stride + per, ow = (u64)nsum * per;
-    for (const u64* o : {out0, out1})
-        if (words_overlap(o, ow, x0, xw) || words_overlap(o, ow, x1, xw) ||
-            words_overlap(o, ow, diag, ((u64)nsum * nterm - 1) * diag_stride + poly))
-            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
-    if (words_overlap(out0, ow, out1, ow)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
-    KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    const u64 xw = (u64)(nterm - 1) * x_stride + per;
+    RCCHK(outputs_check(out0, out1, (u64)nsum * per,
+                        {{x0, xw}, {x1, xw}, {diag, ((u64)nsum * nterm - 1) * diag_stride + poly}}));
     std::vector<u32> rows(nsum);
     for (u32 j = 0; j < nsum; j++) rows[j] = j;
     return lt_inner_run(k, L, nterm, x0, x1, x_stride, diag, diag_stride, present, rows.data(), nsum, out0, out1,
@@ -839,12 +886,10 @@ static int lt_outer_run(ofhe_ks_t k, KsLevel* L, const u64* digits, u32 nset, co
                         const u64* const* key_b, const u64* const* key_a, const u64* add1, u32 nadd, u64* out0,
                         u64* out1, u32 batch, hipStream_t s) {
     const u32 towers = L->size_ql + k->size_p;
-    const u64 poly = (u64)towers << k->log_n, nthreads = (u64)batch * poly;
-    const u64 key_stride = (u64)(k->size_q + k->size_p) << k->log_n;
-    const dim3 g((u32)((nthreads + 255) / 256)), blk(256);
-    u32 j0 = 0;
-    do {
-        const u32 ns = std::min(KS_ROT_CAP, nset - j0);
+    const u64 poly = k->words_qp(L->size_ql), nthreads = batch * poly, key_stride = k->key_stride();
+    dim3 g, blk(256);
+    RCCHK(coeff_grid(nthreads, &g));
+    return rot_chunks(nset, true, [&](u32 j0, u32 ns) {
         LtRot R{};
         for (u32 j = 0; j < ns; j++) {
             R.kb[j] = key_b[j0 + j];
@@ -858,10 +903,8 @@ static int lt_outer_run(ofhe_ks_t k, KsLevel* L, const u64* digits, u32 nset, co
                                j0 ? 1u : 0u);
         };
         if (!with_int<1, 2, 3, 4>((int)L->beta, launch)) launch(std::integral_constant<int, 0>{});
-        RCCHK(post_launch());
-        j0 += ns;
-    } while (j0 < nset);
-    return OFHE_OK;
+        return post_launch();
+    });
 }
 
 int ofhe_hip_ks_fast_rotation_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t nset, const uint64_t* digits,
@@ -873,19 +916,11 @@ int ofhe_hip_ks_fast_rotation_ext_sum(ofhe_ks_t k, uint32_t size_ql, uint32_t ns
     if (nset == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nset and batch must be >= 1");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
     if ((addend1 == nullptr) != (nadd == 0)) return fail(OFHE_ERR_ARG, "addend1 and nadd must be given together");
-    for (u32 j = 0; j < nset; j++) {
-        if (!key_b[j] || !key_a[j]) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
-        if (auto_index[j] % 2 == 0) return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
-    }
-    RCCHK(ks_check(k, size_ql, batch));
+    RCCHK(rot_list_check(nset, auto_index, key_b, key_a));
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
-    const u64 per = (u64)batch * (size_ql + k->size_p) << k->log_n;
-    for (const u64* o : {(const u64*)out0, (const u64*)out1})
-        if (words_overlap(o, per, digits, (u64)nset * L->beta * per) ||
-            (addend1 && words_overlap(o, per, addend1, (u64)nadd * per)))
-            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
-    if (words_overlap(out0, per, out1, per)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    const u64 per = batch * k->words_qp(size_ql);
+    RCCHK(outputs_check(out0, out1, per, {{digits, (u64)nset * L->beta * per}, {addend1, (u64)nadd * per}}));
     return lt_outer_run(k, L, digits, nset, auto_index, key_b, key_a, addend1, nadd, out0, out1, batch,
                         pick(stream));
 }
@@ -901,30 +936,19 @@ int ofhe_hip_ks_bsgs_transform(ofhe_ks_t k, uint32_t size_ql, const ofhe_bsgs* t
     const u32 nb = tr->nbaby, ng = tr->ngiant;
     if (nb == 0 || ng == 0 || batch == 0) return fail(OFHE_ERR_ARG, "nbaby, ngiant and batch must be >= 1");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
-    for (u32 i = 0; i < nb + ng; i++)
-        if ((i < nb ? tr->baby_index[i] : tr->giant_index[i - nb]) % 2 == 0)
-            return fail(OFHE_ERR_ARG, "Automorphism index not odd");  // poly-impl.h:333-334
-    RCCHK(ks_check(k, size_ql, batch));
-    const u32 l = size_ql, P = k->size_p;
-    const u64 N = 1ull << k->log_n, poly = (u64)(l + P) * N, per = (u64)batch * poly, qper = (u64)batch * l * N;
-    if (tr->diag_stride < poly) return fail(OFHE_ERR_ARG, "diag_stride smaller than one diagonal");
-    const u32 m2 = (u32)(2 * N - 1);
-    auto is_id = [&](u32 idx) { return (idx & m2) == 1; };
-    for (u32 i = 0; i < nb + ng; i++) {
-        const bool baby = i < nb;
-        const u32 r = baby ? i : i - nb, idx = baby ? tr->baby_index[r] : tr->giant_index[r];
-        const u64* kb = baby ? tr->baby_key_b[r] : tr->giant_key_b[r];
-        const u64* ka = baby ? tr->baby_key_a[r] : tr->giant_key_a[r];
-        if (!is_id(idx) && (!kb || !ka)) return fail(OFHE_ERR_ARG, "NULL evaluation key pointer");
-    }
-    const u64 dw = ((u64)nb * ng - 1) * tr->diag_stride + poly;
-    for (const u64* o : {(const u64*)out0, (const u64*)out1})
-        if (words_overlap(o, qper, c0, qper) || words_overlap(o, qper, c1, qper) ||
-            words_overlap(o, qper, tr->diag, dw))
-            return fail(OFHE_ERR_ARG, "outputs must not alias inputs");
-    if (words_overlap(out0, qper, out1, qper)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    RCCHK(rot_list_check(nb, tr->baby_index, nullptr, nullptr));
+    RCCHK(rot_list_check(ng, tr->giant_index, nullptr, nullptr));
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    const u32 l = size_ql;
+    const u64 poly = k->words_qp(l), per = batch * poly, qw = k->words_q(l), qper = batch * qw;
+    if (tr->diag_stride < poly) return fail(OFHE_ERR_ARG, "diag_stride smaller than one diagonal");
+    const u32 m2 = (u32)((2ull << k->log_n) - 1);
+    auto is_id = [&](u32 idx) { return rot_is_id(idx, m2); };
+    RCCHK(rot_list_check(nb, tr->baby_index, tr->baby_key_b, tr->baby_key_a, m2));
+    RCCHK(rot_list_check(ng, tr->giant_index, tr->giant_key_b, tr->giant_key_a, m2));
+    RCCHK(outputs_check(out0, out1, qper,
+                        {{c0, qper}, {c1, qper}, {tr->diag, ((u64)nb * ng - 1) * tr->diag_stride + poly}}));
     hipStream_t s = pick(stream);
     ModDownArgs A;
     RCCHK(ks_md_args(k, L, t, &A));
@@ -995,7 +1019,7 @@ int ofhe_hip_ks_bsgs_transform(ofhe_ks_t k, uint32_t size_ql, const ofhe_bsgs* t
     u64* mdid = md1 + (u64)nrot * qper;
     if (nrot) {
         u64* const outs[2] = {md0, md1};
-        RCCHK(mod_down_run(A, i0r, poly, outs, 2, (u64)l * N, nrot * batch, s));
+        RCCHK(mod_down_run(A, i0r, poly, outs, 2, qw, nrot * batch, s));
     }
 
     // 5-6. the rotated giants' second elements decomposed as one batch (1544),
@@ -1012,17 +1036,16 @@ int ofhe_hip_ks_bsgs_transform(ofhe_ks_t k, uint32_t size_ql, const ofhe_bsgs* t
     // of launches over 2 + nid polynomials per entry; then += first (1551)
     std::vector<u64*> outs{out0, out1};
     for (u32 j = 0; j < nid; j++) outs.push_back(mdid + (u64)j * qper);
-    RCCHK(mod_down_run(A, ou.w(), poly, outs.data(), 2 + nid, (u64)l * N, batch, s));
-    for (u32 j0 = 0, first = 1; first || j0 < nrot; first = 0) {
-        const u32 ns = std::min(KS_ROT_CAP, nrot - j0);
+    RCCHK(mod_down_run(A, ou.w(), poly, outs.data(), 2 + nid, qw, batch, s));
+    dim3 g;
+    RCCHK(coeff_grid(qper, &g));
+    return rot_chunks(nrot, true, [&](u32 j0, u32 ns) {
         LtIdx I{};
         for (u32 j = 0; j < ns; j++) I.k[j] = gidx[j0 + j];
-        hipLaunchKernelGGL(k_lt_first, dim3((u32)((qper + 255) / 256)), dim3(256), 0, s, L->d_tow, out0,
-                           md0 + (u64)j0 * qper, I, ns, mdid, first ? nid : 0u, out0, qper, k->log_n, l);
-        RCCHK(post_launch());
-        j0 += ns;
-    }
-    return OFHE_OK;
+        hipLaunchKernelGGL(k_lt_first, g, dim3(256), 0, s, L->d_tow, out0, md0 + (u64)j0 * qper, I, ns, mdid,
+                           j0 ? 0u : nid, out0, qper, k->log_n, l);
+        return post_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1070,6 +1093,39 @@ static int plan_table(ofhe_plan_t p, const std::vector<u64>& words, const u64** 
                         [&]() -> const std::vector<u64>& { return words; });
 }
 
+// The rescaling tables of L towers q[0..L), the one place that knows their
+// layout and algebra.  A row of sw (SwArgs::tab) is six words
+// [q, w, w', a, a', 0], of which the device reads w as tab[6 t + 1]; a row of sc
+// is the TowerScalar [q, a, a'] of the forward-subtract pass, which only
+// evaluation form runs.  w multiplies the lifted last tower:
+//   SW_AXPY (rescale)     coefficient form c,  evaluation form -(c a^-1)
+//   SW_XPYA (mod-reduce)  coefficient form t,  evaluation form -t
+//   SW_SCALE              1: the bare lift (CRTDecompose), with neither a nor sc
+// and a, a' stand in sw where k_switch_scale itself multiplies by a (coefficient
+// form) and in every mod-reduce row.  c and a are per tower, reduced here; a[i]
+// must be invertible mod q[i] for SW_AXPY in evaluation form.
+enum { SWR_Q = 0, SWR_W = 1, SWR_A = 3, SWR_WORDS = 6 };
+static RsTab rs_build(const u64* q, u32 L, int mode, bool eval, const u64* c, const u64* a, u64 t, u64 pre = 1) {
+    RsTab T;
+    T.mode = mode;
+    T.pre = pre;
+    T.sw.assign(SWR_WORDS * (size_t)L, 0);
+    for (u32 i = 0; i < L; i++) {
+        const u64 qi = q[i];
+        u64* row = &T.sw[SWR_WORDS * (size_t)i];
+        u64 w = 1;
+        if (mode == SW_AXPY) w = eval ? qi - mulmod(c[i] % qi, invmod(a[i] % qi, qi), qi) : c[i];
+        if (mode == SW_XPYA) w = eval ? qi - t % qi : t;
+        const TowerScalar W = scalar_of(qi, w);
+        row[SWR_Q] = qi, row[SWR_W] = W.s, row[SWR_W + 1] = W.sp;
+        if (mode == SW_SCALE) continue;
+        const TowerScalar S = scalar_of(qi, a[i]);
+        if (mode == SW_XPYA || !eval) row[SWR_A] = S.s, row[SWR_A + 1] = S.sp;
+        if (eval) T.sc.insert(T.sc.end(), {S.q, S.s, S.sp});
+    }
+    return T;
+}
+
 static int rescale_check(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, const u64* out, u64 os, u32 batch) {
     if (!p || !p->ctx) return fail(OFHE_ERR_STATE, "plan is NULL or destroyed");
     if (!x || !out || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
@@ -1090,14 +1146,12 @@ static int rescale_check(ofhe_plan_t p, u32 towers, const u64* x, u64 xs, const 
     return OFHE_OK;
 }
 
-// shared tail: sw[6 L] for k_switch_scale, sc[3 L] (q, a, a') for the
-// forward-subtract (evaluation form).  nelem elements x[e] -> out[e] of `batch`
+// shared tail, on the tables T of rs_build.  nelem elements x[e] -> out[e] of `batch`
 // entries each (evaluation form when nelem > 1): the last towers' INTT (one
 // launch when the elements follow one another), the lift and the column pass
 // run over nelem * batch polynomials, the pass that writes out[e] per element.
 static int rescale_run(ofhe_plan_t p, u32 towers, const u64* const* xv, u64 xs, u64* const* outv, u64 os, u32 nelem,
-                       bool eval, int mode, const std::vector<u64>& sw, const std::vector<u64>& sc, u64 pre,
-                       u32 batch, hipStream_t s) {
+                       bool eval, const RsTab& T, u32 batch, hipStream_t s) {
     HIPCHK(hipSetDevice(p->ctx->device));
     const u64* x = xv[0];
     u64* out = outv[0];
@@ -1105,13 +1159,13 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* const* xv, u64 xs, 
     const u32 L = towers - 1, log_n = p->log_n;
     const u64 N = 1ull << log_n;
     const u64 *dsw = nullptr, *dsc = nullptr;
-    RCCHK(plan_table(p, sw, &dsw));
-    if (eval) RCCHK(plan_table(p, sc, &dsc));
+    RCCHK(plan_table(p, T.sw, &dsw));
+    if (eval) RCCHK(plan_table(p, T.sc, &dsc));
     const u64 ql = p->q[L];
     SwArgs A{};
     A.tab = dsw;
     A.ql = ql;
-    A.pre = pre % ql;
+    A.pre = T.pre % ql;
     A.pre_p = shoup_pre(A.pre, ql);
     if (A.pre == 1) A.pre_p = 0;
     A.log_n = log_n;
@@ -1126,13 +1180,13 @@ static int rescale_run(ofhe_plan_t p, u32 towers, const u64* const* xv, u64 xs, 
         A.xstride = xs;
         A.y = out;
         A.ystride = os;
-        with_int<SW_AXPY, SW_XPYA>(mode, [&](auto m) {
+        with_int<SW_AXPY, SW_XPYA>(T.mode, [&](auto m) {
             hipLaunchKernelGGL(k_switch_scale<decltype(m)::value>, g, dim3(256), 0, s, A, bpr);
         });
         RCCHK(post_launch());
         // DropLastElementAndScale switches the coefficient-form towers to
         // evaluation form (dcrtpoly-impl.h:765-766); ModReduce does not
-        if (mode == SW_AXPY) return plan_ntt_range(p, false, 0, L, out, out, os, os, batch, s);
+        if (T.mode == SW_AXPY) return plan_ntt_range(p, false, 0, L, out, out, os, os, batch, s);
         return OFHE_OK;
     }
     Scratch sl, sy;
@@ -1185,22 +1239,11 @@ int ofhe_hip_drop_last_and_scale(ofhe_plan_t p, uint32_t towers, const uint64_t*
     RCCHK(rescale_check(p, towers, x, x_stride, out, out_stride, batch));
     if (!ql_ql_inv_modql_divql_modq || !ql_inv_modq) return fail(OFHE_ERR_ARG, "NULL constants");
     const u32 L = towers - 1;
-    std::vector<u64> sw(6 * (size_t)L, 0), sc(3 * (size_t)L, 0);
-    for (u32 i = 0; i < L; i++) {
-        const u64 q = p->q[i], c = ql_ql_inv_modql_divql_modq[i] % q, a = ql_inv_modq[i] % q;
-        if (eval_form) {
-            if (a == 0) return fail(OFHE_ERR_ARG, "ql_inv_modq[" + std::to_string(i) + "] is not invertible mod q_i");
-            const u64 w = (q - mulmod(c, invmod(a, q), q)) % q;
-            const TowerScalar W = scalar_of(q, w), S = scalar_of(q, a);
-            sw[6 * i] = q, sw[6 * i + 1] = W.s, sw[6 * i + 2] = W.sp;
-            sc[3 * i] = q, sc[3 * i + 1] = S.s, sc[3 * i + 2] = S.sp;
-        } else {
-            const TowerScalar W = scalar_of(q, c), S = scalar_of(q, a);
-            sw[6 * i] = q, sw[6 * i + 1] = W.s, sw[6 * i + 2] = W.sp, sw[6 * i + 3] = S.s, sw[6 * i + 4] = S.sp;
-        }
-    }
-    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, SW_AXPY, sw, sc, 1, batch,
-                       pick(stream));
+    for (u32 i = 0; eval_form && i < L; i++)
+        if (ql_inv_modq[i] % p->q[i] == 0)
+            return fail(OFHE_ERR_ARG, "ql_inv_modq[" + std::to_string(i) + "] is not invertible mod q_i");
+    const RsTab T = rs_build(p->q.data(), L, SW_AXPY, eval_form != 0, ql_ql_inv_modql_divql_modq, ql_inv_modq, 0);
+    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, T, batch, pick(stream));
 }
 
 int ofhe_hip_mod_reduce(ofhe_plan_t p, uint32_t towers, const uint64_t* x, uint64_t x_stride, uint64_t* out,
@@ -1208,16 +1251,8 @@ int ofhe_hip_mod_reduce(ofhe_plan_t p, uint32_t towers, const uint64_t* x, uint6
                         const uint64_t* ql_inv_modq, uint32_t batch, void* stream) {
     RCCHK(rescale_check(p, towers, x, x_stride, out, out_stride, batch));
     if (!ql_inv_modq) return fail(OFHE_ERR_ARG, "NULL constants");
-    const u32 L = towers - 1;
-    std::vector<u64> sw(6 * (size_t)L, 0), sc(3 * (size_t)L, 0);
-    for (u32 i = 0; i < L; i++) {
-        const u64 q = p->q[i], tq = t % q, a = ql_inv_modq[i] % q;
-        const TowerScalar W = scalar_of(q, eval_form ? (q - tq) % q : tq), S = scalar_of(q, a);
-        sw[6 * i] = q, sw[6 * i + 1] = W.s, sw[6 * i + 2] = W.sp, sw[6 * i + 3] = S.s, sw[6 * i + 4] = S.sp;
-        sc[3 * i] = q, sc[3 * i + 1] = S.s, sc[3 * i + 2] = S.sp;
-    }
-    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, SW_XPYA, sw, sc,
-                       neg_t_inv_modq, batch, pick(stream));
+    const RsTab T = rs_build(p->q.data(), towers - 1, SW_XPYA, eval_form != 0, nullptr, ql_inv_modq, t, neg_t_inv_modq);
+    return rescale_run(p, towers, &x, x_stride, &out, out_stride, 1, eval_form != 0, T, batch, pick(stream));
 }
 
 // ---------------------------------------------------------------------------
@@ -1237,13 +1272,8 @@ int ofhe_hip_bv_precompute(ofhe_plan_t p, uint32_t towers, const uint64_t* c, ui
     hipStream_t s = pick(stream);
     const u32 T = towers, log_n = p->log_n;
     const u64 N = 1ull << log_n, TN = (u64)T * N;
-    std::vector<u64> sw(6 * (size_t)T, 0);
-    for (u32 k = 0; k < T; k++) {
-        const TowerScalar W = scalar_of(p->q[k], 1);
-        sw[6 * k] = p->q[k], sw[6 * k + 1] = W.s, sw[6 * k + 2] = W.sp;
-    }
     const u64* dsw = nullptr;
-    RCCHK(plan_table(p, sw, &dsw));
+    RCCHK(plan_table(p, rs_build(p->q.data(), T, SW_SCALE, true, nullptr, nullptr, 0).sw, &dsw));
     Scratch sc;  // c in coefficient form
     RCCHK(sc.alloc((size_t)batch * TN * 8, s, p->ctx));
     RCCHK(plan_ntt_range(p, true, 0, T, c, sc.w(), TN, TN, batch, s));
@@ -1314,8 +1344,8 @@ int ofhe_hip_bv_core(ofhe_plan_t p, uint32_t towers, const uint64_t* digits, con
 // BGV: negtInvModq = -t^-1 mod q_l; CKKS: QlQlInvModqlDivqlModq[i] = q_i - a_i.
 // With Q = prod_{j<l} q_j and b = Q^-1 mod q_l, b Q = 1 + k q_l and the table is
 // k = floor(b Q / q_l) mod q_i; Q = 0 mod q_i gives k q_l = -1, k = -a_i.
-// The words are those ofhe_hip_drop_last_and_scale / ofhe_hip_mod_reduce build
-// from the caller's constants (evaluation form).
+// rs_build turns them into the words ofhe_hip_drop_last_and_scale /
+// ofhe_hip_mod_reduce build from the caller's constants (evaluation form).
 static int rs_tables(ofhe_ks_t k, u32 towers, u64 t, const RsTab** out) {
     std::lock_guard<std::mutex> lk(k->mu);
     const auto key = std::make_pair(towers, t);
@@ -1323,23 +1353,13 @@ static int rs_tables(ofhe_ks_t k, u32 towers, u64 t, const RsTab** out) {
     if (it == k->rescale.end()) {
         const u32 L = towers - 1;
         const u64 ql = k->q[L];
-        RsTab T;
-        T.sw.assign(6 * (size_t)L, 0);
-        T.sc.assign(3 * (size_t)L, 0);
+        std::vector<u64> a(L), c(L);
         for (u32 i = 0; i < L; i++) {
-            const u64 q = k->q[i], a = invmod(ql % q, q);
-            u64 w;
-            if (t)
-                w = (q - t % q) % q;
-            else  // -(c a^-1) with c = q - a and a^-1 = q_l mod q_i
-                w = (q - mulmod(q - a, ql % q, q)) % q;
-            const TowerScalar W = scalar_of(q, w), S = scalar_of(q, a);
-            T.sw[6 * i] = q, T.sw[6 * i + 1] = W.s, T.sw[6 * i + 2] = W.sp;
-            if (t) T.sw[6 * i + 3] = S.s, T.sw[6 * i + 4] = S.sp;
-            T.sc[3 * i] = q, T.sc[3 * i + 1] = S.s, T.sc[3 * i + 2] = S.sp;
+            a[i] = invmod(ql % k->q[i], k->q[i]);
+            c[i] = k->q[i] - a[i];
         }
-        T.pre = t ? ql - invmod(t % ql, ql) : 1;
-        it = k->rescale.emplace(key, std::move(T)).first;
+        it = k->rescale.emplace(key, rs_build(k->q.data(), L, t ? SW_XPYA : SW_AXPY, true, c.data(), a.data(), t,
+                                              t ? ql - invmod(t % ql, ql) : 1)).first;
     }
     *out = &it->second;
     return OFHE_OK;
@@ -1371,22 +1391,19 @@ static bool she_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the levels in between live in scratch, in place from the second on
 static int rescale_levels(ofhe_ks_t k, u32 l, int scheme, u64 t, u32 levels, u32 nelem, const u64* const* x,
                           u64* const* out, u32 batch, hipStream_t s) {
-    const u64 N = 1ull << k->log_n;
     std::vector<const RsTab*> tabs(levels);
     for (u32 lv = 0; lv < levels; lv++) RCCHK(rs_tables(k, l - lv, scheme == OFHE_SHE_BGV ? t : 0, &tabs[lv]));
     Scratch mid;
-    const u64 ms = (u64)(l - 1) * N;
+    const u64 ms = k->words_q(l - 1);
     if (levels > 1) RCCHK(mid.alloc((size_t)nelem * batch * ms * 8, s, k->ctx));
     std::vector<const u64*> cur(x, x + nelem);
     std::vector<u64*> nxt(nelem);
-    u64 cs = (u64)l * N;
+    u64 cs = k->words_q(l);
     for (u32 lv = 0; lv < levels; lv++) {
         const bool last = lv + 1 == levels;
-        const u64 os = last ? (u64)(l - levels) * N : ms;
+        const u64 os = last ? k->words_q(l - levels) : ms;
         for (u32 e = 0; e < nelem; e++) nxt[e] = last ? out[e] : mid.w() + (u64)e * batch * ms;
-        RCCHK(rescale_run(k->plan, l - lv, cur.data(), cs, nxt.data(), os, nelem, true,
-                          scheme == OFHE_SHE_BGV ? SW_XPYA : SW_AXPY, tabs[lv]->sw, tabs[lv]->sc, tabs[lv]->pre, batch,
-                          s));
+        RCCHK(rescale_run(k->plan, l - lv, cur.data(), cs, nxt.data(), os, nelem, true, *tabs[lv], batch, s));
         cur.assign(nxt.begin(), nxt.end());
         cs = os;
     }
@@ -1407,7 +1424,7 @@ int ofhe_hip_ks_rescale(ofhe_ks_t k, uint32_t size_ql, int scheme, uint64_t t, u
     if (levels >= size_ql) return fail(OFHE_ERR_ARG, "levels must be below size_ql");
     RCCHK(ks_check(k, size_ql, batch));
     RCCHK(she_t_check(k, size_ql, t, false));
-    const u64 N = 1ull << k->log_n, xw = (u64)batch * size_ql * N, ow = (u64)batch * (size_ql - levels) * N;
+    const u64 xw = batch * k->words_q(size_ql), ow = batch * k->words_q(size_ql - levels);
     for (u32 e = 0; e < nelem; e++) {
         for (u32 j = 0; j < nelem; j++)
             if (words_overlap(out[e], ow, x[j], xw) || (j != e && words_overlap(out[e], ow, out[j], ow)))
@@ -1430,12 +1447,11 @@ int ofhe_hip_ks_relinearize(ofhe_ks_t k, uint32_t size_ql, uint32_t nelem, const
     }
     if (!she_aligned(out0) || !she_aligned(out1)) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
-    RCCHK(ks_check(k, size_ql, batch));
-    RCCHK(she_t_check(k, size_ql, t, true));
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
-    const u64 N = 1ull << k->log_n, w = (u64)batch * size_ql * N, kw = (u64)L->beta * (k->size_q + k->size_p) * N;
-    if (words_overlap(out0, w, out1, w)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    RCCHK(she_t_check(k, size_ql, t, true));
+    const u64 w = batch * k->words_q(size_ql), kw = L->beta * k->key_stride();
+    RCCHK(outputs_apart(out0, out1, w));
     u64* const outs[2] = {out0, out1};
     for (u32 o = 0; o < 2; o++) {
         for (u32 j = 0; j < nelem; j++)
@@ -1464,14 +1480,13 @@ int ofhe_hip_ks_eval_mult(ofhe_ks_t k, uint32_t size_ql, const uint64_t* c0, con
     RCCHK(she_scheme_check(scheme, t));
     if (levels >= size_ql) return fail(OFHE_ERR_ARG, "levels must be below size_ql");
     if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
-    RCCHK(ks_check(k, size_ql, batch));
-    RCCHK(she_t_check(k, size_ql, t, true));
     KsLevel* L = nullptr;
-    RCCHK(level_get(k, size_ql, &L));
+    RCCHK(ks_enter(k, size_ql, batch, &L));
+    RCCHK(she_t_check(k, size_ql, t, true));
     const u32 l = size_ql;
-    const u64 N = 1ull << k->log_n, w = (u64)batch * l * N, ow = (u64)batch * (l - levels) * N;
-    const u64 kw = (u64)L->beta * (k->size_q + k->size_p) * N;
-    if (words_overlap(out0, ow, out1, ow)) return fail(OFHE_ERR_ARG, "out0 and out1 overlap");
+    const u64 N = 1ull << k->log_n, w = batch * k->words_q(l), ow = batch * k->words_q(l - levels);
+    const u64 kw = L->beta * k->key_stride();
+    RCCHK(outputs_apart(out0, out1, ow));
     for (const u64* o : {out0, out1}) {
         // the tensor product consumes the operands before anything is written: an
         // output may start where an operand starts (the InPlace forms)
