@@ -261,20 +261,75 @@ private:
 // reference's static per-modulus maps keep their tables (transformnat.h:352-368,
 // filled in PreCompute, transformnat-impl.h:708-763).
 // ---------------------------------------------------------------------------
+// Handle<S, destroy>: the one owner of a C-ABI handle -- move-only, destroyed
+// exactly once by the ABI's own destroy function; get() is the raw handle.
+template <auto Destroy>
+struct HandleDeleter {
+    template <class S>
+    void operator()(S* h) const {
+        Destroy(h);
+    }
+};
+template <class S, auto Destroy>
+using Handle = std::unique_ptr<S, HandleDeleter<Destroy>>;
+
+// Cache<Key, T>::get(key, build): the one get-or-create -- a process-wide map
+// under a mutex per call site; build() runs on a miss, with the lock held, and
+// its result is kept for the process lifetime.  Always inlined, so a hit costs
+// what the hand-written lookups did (profiles/adapter_host_ab.json).
+template <class Key, class T>
+struct Cache {
+    template <class F>
+    [[gnu::always_inline]] static inline std::shared_ptr<T> get(const Key& key, F&& build) {
+        static std::mutex mu;
+        static std::map<Key, std::shared_ptr<T>> map;
+        std::lock_guard<std::mutex> lk(mu);
+        auto& e = map[key];
+        if (!e) e = build();
+        return e;
+    }
+};
+
+// NamedStore<T>: the one string-keyed table of shared objects (put / find /
+// erase under a mutex); find returns null for an unknown id.
+template <class T>
+struct NamedStore {
+    static void put(const std::string& id, std::shared_ptr<const T> v) {
+        std::lock_guard<std::mutex> lk(mu());
+        map()[id] = std::move(v);
+    }
+    static std::shared_ptr<const T> find(const std::string& id) {
+        std::lock_guard<std::mutex> lk(mu());
+        auto it = map().find(id);
+        return it == map().end() ? nullptr : it->second;
+    }
+    static void erase(const std::string& id) {
+        std::lock_guard<std::mutex> lk(mu());
+        map().erase(id);
+    }
+
+private:
+    static std::mutex& mu() {
+        static std::mutex m;
+        return m;
+    }
+    static std::map<std::string, std::shared_ptr<const T>>& map() {
+        static std::map<std::string, std::shared_ptr<const T>> m;
+        return m;
+    }
+};
+
 class PlanHandle {
 public:
     PlanHandle(HipManager* m, uint32_t log_n, const std::vector<uint64_t>& q, const std::vector<uint64_t>& r) {
-        check(ofhe_hip_plan_create(m->ctx(), log_n, (uint32_t)q.size(), q.data(), r.data(), &p_), "PlanCache");
+        ofhe_plan_t p = nullptr;
+        check(ofhe_hip_plan_create(m->ctx(), log_n, (uint32_t)q.size(), q.data(), r.data(), &p), "PlanCache");
+        p_.reset(p);
     }
-    ~PlanHandle() {
-        if (p_) ofhe_hip_plan_destroy(p_);
-    }
-    PlanHandle(const PlanHandle&) = delete;
-    PlanHandle& operator=(const PlanHandle&) = delete;
-    ofhe_plan_t get() const { return p_; }
+    ofhe_plan_t get() const { return p_.get(); }
 
 private:
-    ofhe_plan_t p_ = nullptr;
+    Handle<ofhe_plan_s, ofhe_hip_plan_destroy> p_;
 };
 
 class PlanCache {
@@ -284,12 +339,8 @@ public:
         if (moduli.size() != roots.size() || moduli.empty()) throw math_error("PlanCache: moduli/roots size mismatch");
         // the manager's statics first: destroyed after the cached plans
         HipManager* m = HipManager::getHip(device);
-        static std::mutex mu;
-        static std::map<Key, std::shared_ptr<PlanHandle>> plans;
-        std::lock_guard<std::mutex> lk(mu);
-        auto& e = plans[Key{device, log_n, moduli, roots}];
-        if (!e) e = std::make_shared<PlanHandle>(m, log_n, moduli, roots);
-        return e;
+        return Cache<Key, PlanHandle>::get(Key{device, log_n, moduli, roots},
+                                           [&] { return std::make_shared<PlanHandle>(m, log_n, moduli, roots); });
     }
 
 private:
@@ -413,6 +464,11 @@ private:
 // Parameters: (cyclotomic order, moduli, roots) as ILDCRTParams; the NTT plan
 // comes from PlanCache, so parameter objects over the same basis share it.
 // ---------------------------------------------------------------------------
+// words [first, first + count) of a per-tower list: the one place a basis is cut
+inline std::vector<uint64_t> towers_of(const std::vector<uint64_t>& v, size_t first, size_t count) {
+    return std::vector<uint64_t>(v.begin() + first, v.begin() + first + count);
+}
+
 class DCRTParams {
 public:
     DCRTParams(uint32_t cyclotomic_order, std::vector<uint64_t> moduli, std::vector<uint64_t> roots,
@@ -435,6 +491,18 @@ public:
     const std::vector<uint64_t>& Roots() const { return r_; }
     ofhe_plan_t plan() const { return plan_->get(); }
     HipManager* manager() const { return mgr_; }
+    // the params of towers [first, first + count), and of these towers followed
+    // by o's (cached plans of those bases)
+    std::shared_ptr<DCRTParams> Slice(size_t first, size_t count) const {
+        return std::make_shared<DCRTParams>(m_, towers_of(q_, first, count), towers_of(r_, first, count),
+                                            mgr_->device());
+    }
+    std::shared_ptr<DCRTParams> Join(const DCRTParams& o) const {
+        std::vector<uint64_t> q(q_), r(r_);
+        q.insert(q.end(), o.q_.begin(), o.q_.end());
+        r.insert(r.end(), o.r_.begin(), o.r_.end());
+        return std::make_shared<DCRTParams>(m_, std::move(q), std::move(r), mgr_->device());
+    }
 
 private:
     uint32_t m_, log_n_ = 0;
@@ -442,6 +510,13 @@ private:
     HipManager* mgr_;
     std::shared_ptr<PlanHandle> plan_;
 };
+
+// DropLastElement `levels` times (dcrtpoly-impl.h:719-728): the params of the
+// shorter chain
+inline std::shared_ptr<DCRTParams> lowered(const DCRTParams& p, size_t levels) {
+    if (levels >= p.Towers()) throw math_error("Removing last element of DCRTPoly object renders it invalid!");
+    return p.Slice(0, p.Towers() - levels);
+}
 
 enum class Format { EVALUATION = 0, COEFFICIENT = 1 };
 
@@ -470,6 +545,14 @@ public:
     }
     DCRTPolyHip(DCRTPolyHip&&) = default;
     DCRTPolyHip& operator=(DCRTPolyHip&&) = default;
+    // the uninitialised result of an op, over p in format f, and a pair of them
+    static DCRTPolyHip result(std::shared_ptr<DCRTParams> p, Format f, uint32_t batch) {
+        return DCRTPolyHip(std::move(p), f, batch, Uninit{});
+    }
+    static std::pair<DCRTPolyHip, DCRTPolyHip> result_pair(const std::shared_ptr<DCRTParams>& p, Format f,
+                                                           uint32_t batch) {
+        return {result(p, f, batch), result(p, f, batch)};
+    }
 
     const std::shared_ptr<DCRTParams>& GetParams() const { return p_; }
     Format GetFormat() const { return f_; }
@@ -510,25 +593,10 @@ public:
         if (f != f_) SwitchFormat();
     }
 
-    DCRTPolyHip Plus(const DCRTPolyHip& rhs) const {
-        check_compat(rhs, "Plus", false);
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
-        check(ofhe_hip_modadd_vv(p_->plan(), data(), rhs.data(), r.data(), batch_, nullptr), "Plus");
-        return r;
-    }
-    DCRTPolyHip Minus(const DCRTPolyHip& rhs) const {
-        check_compat(rhs, "Minus", false);
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
-        check(ofhe_hip_modsub_vv(p_->plan(), data(), rhs.data(), r.data(), batch_, nullptr), "Minus");
-        return r;
-    }
+    DCRTPolyHip Plus(const DCRTPolyHip& rhs) const { return binary("Plus", ofhe_hip_modadd_vv, rhs, false); }
+    DCRTPolyHip Minus(const DCRTPolyHip& rhs) const { return binary("Minus", ofhe_hip_modsub_vv, rhs, false); }
     // Times (dcrtpoly.h:185-200): EVALUATION format only
-    DCRTPolyHip Times(const DCRTPolyHip& rhs) const {
-        check_compat(rhs, "Times", true);
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
-        check(ofhe_hip_modmul_vv(p_->plan(), data(), rhs.data(), r.data(), batch_, nullptr), "Times");
-        return r;
-    }
+    DCRTPolyHip Times(const DCRTPolyHip& rhs) const { return binary("Times", ofhe_hip_modmul_vv, rhs, true); }
     // DropLastElementAndScale (dcrtpoly-impl.h:746-768; CKKS / BFV rescaling):
     // one tower fewer, on the params of the shorter chain.  The reference keeps
     // m_format while its coefficient-form towers come back in evaluation form
@@ -538,8 +606,7 @@ public:
         const size_t T = p_->Towers(), n = p_->GetRingDimension();
         if (QlQlInvModqlDivqlModq.size() + 1 < T || qlInvModq.size() + 1 < T)
             throw math_error("DropLastElementAndScale: one constant per remaining tower required");
-        auto lp = lower_params();
-        DCRTPolyHip r(lp, Format::EVALUATION, batch_, Uninit{});
+        DCRTPolyHip r = result(lowered(*p_, 1), Format::EVALUATION, batch_);
         check(ofhe_hip_drop_last_and_scale(p_->plan(), (uint32_t)T, data(), T * n, r.data(), (T - 1) * n,
                                            f_ == Format::EVALUATION, QlQlInvModqlDivqlModq.data(), qlInvModq.data(),
                                            batch_, nullptr),
@@ -551,8 +618,7 @@ public:
     void ModReduce(uint64_t t, uint64_t negtInvModq, const std::vector<uint64_t>& qlInvModq) {
         const size_t T = p_->Towers(), n = p_->GetRingDimension();
         if (qlInvModq.size() + 1 < T) throw math_error("ModReduce: one constant per remaining tower required");
-        auto lp = lower_params();
-        DCRTPolyHip r(lp, f_, batch_, Uninit{});
+        DCRTPolyHip r = result(lowered(*p_, 1), f_, batch_);
         check(ofhe_hip_mod_reduce(p_->plan(), (uint32_t)T, data(), T * n, r.data(), (T - 1) * n,
                                   f_ == Format::EVALUATION, t, negtInvModq, qlInvModq.data(), batch_, nullptr),
               "ModReduce");
@@ -570,10 +636,7 @@ public:
 
     // Times(const std::vector<NativeInteger>&): one scalar per tower (Shoup)
     DCRTPolyHip Times(const std::vector<uint64_t>& scalars) const {
-        if (scalars.size() != p_->Towers()) throw math_error("Times: one scalar per tower required");
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
-        check(ofhe_hip_modmul_scalar(p_->plan(), data(), scalars.data(), r.data(), batch_, nullptr), "Times");
-        return r;
+        return scalar("Times", "scalar", ofhe_hip_modmul_scalar, scalars);
     }
     // Plus / Minus with one integer per tower (dcrtpoly.h:162-163, 182-183;
     // dcrtpoly-impl.h:545-584).  PolyImpl::Plus(Integer) adds the constant
@@ -582,37 +645,26 @@ public:
     // PolyImpl::Minus(Integer) subtracts from every word in either form
     // (poly-impl.h:223-227), as the reference does.
     DCRTPolyHip Plus(const std::vector<uint64_t>& crt) const {
-        if (crt.size() != p_->Towers()) throw math_error("Plus: one integer per tower required");
+        if (f_ != Format::COEFFICIENT) return scalar("Plus", "integer", ofhe_hip_modadd_scalar, crt);
+        per_tower("Plus", "integer", crt);
         DCRTPolyHip r(*this);
-        if (f_ == Format::COEFFICIENT)
-            check(ofhe_hip_modadd_scalar_at(p_->plan(), r.data(), 0, crt.data(), r.data(), batch_, nullptr), "Plus");
-        else
-            check(ofhe_hip_modadd_scalar(p_->plan(), data(), crt.data(), r.data(), batch_, nullptr), "Plus");
+        check(ofhe_hip_modadd_scalar_at(p_->plan(), r.data(), 0, crt.data(), r.data(), batch_, nullptr), "Plus");
         return r;
     }
     DCRTPolyHip Minus(const std::vector<uint64_t>& crt) const {
-        if (crt.size() != p_->Towers()) throw math_error("Minus: one integer per tower required");
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
-        check(ofhe_hip_modsub_scalar(p_->plan(), data(), crt.data(), r.data(), batch_, nullptr), "Minus");
-        return r;
+        return scalar("Minus", "integer", ofhe_hip_modsub_scalar, crt);
     }
     // Plus / Minus(const Integer&): the same integer in every tower
     DCRTPolyHip Plus(uint64_t v) const { return Plus(std::vector<uint64_t>(p_->Towers(), v)); }
     DCRTPolyHip Minus(uint64_t v) const { return Minus(std::vector<uint64_t>(p_->Towers(), v)); }
     DCRTPolyHip& operator+=(const DCRTPolyHip& rhs) {
-        check_compat(rhs, "operator+=", false);
-        check(ofhe_hip_modadd_vv(p_->plan(), data(), rhs.data(), data(), batch_, nullptr), "operator+=");
-        return *this;
+        return binary_eq("operator+=", ofhe_hip_modadd_vv, rhs, false);
     }
     DCRTPolyHip& operator-=(const DCRTPolyHip& rhs) {
-        check_compat(rhs, "operator-=", false);
-        check(ofhe_hip_modsub_vv(p_->plan(), data(), rhs.data(), data(), batch_, nullptr), "operator-=");
-        return *this;
+        return binary_eq("operator-=", ofhe_hip_modsub_vv, rhs, false);
     }
     DCRTPolyHip& operator*=(const DCRTPolyHip& rhs) {
-        check_compat(rhs, "operator*=", true);
-        check(ofhe_hip_modmul_vv(p_->plan(), data(), rhs.data(), data(), batch_, nullptr), "operator*=");
-        return *this;
+        return binary_eq("operator*=", ofhe_hip_modmul_vv, rhs, true);
     }
     DCRTPolyHip operator+(const DCRTPolyHip& rhs) const { return Plus(rhs); }
     DCRTPolyHip operator-(const DCRTPolyHip& rhs) const { return Minus(rhs); }
@@ -624,14 +676,14 @@ public:
         if (f_ != Format::COEFFICIENT || rhs.f_ != Format::EVALUATION)
             throw not_implemented_error("MulViaNTT: needs COEFFICIENT x EVALUATION");
         check_compat(rhs, "MulViaNTT", false, false);
-        DCRTPolyHip r(p_, Format::COEFFICIENT, batch_, Uninit{});
+        DCRTPolyHip r = result(p_, Format::COEFFICIENT, batch_);
         check(ofhe_hip_ntt_mul_intt(p_->plan(), data(), rhs.data(), r.data(), batch_, nullptr), "MulViaNTT");
         return r;
     }
 
     // AutomorphismTransform(k) (dcrtpoly-impl.h:350-358 -> poly-impl.h:312-365)
     DCRTPolyHip AutomorphismTransform(uint32_t k) const {
-        DCRTPolyHip r(p_, f_, batch_, Uninit{});
+        DCRTPolyHip r = result(p_, f_, batch_);
         check(ofhe_hip_automorphism(p_->plan(), k, f_ == Format::EVALUATION, data(), r.data(), batch_, nullptr),
               "AutomorphismTransform");
         return r;
@@ -730,7 +782,7 @@ public:
             flat.insert(flat.end(), vals.begin(), vals.end());
         }
         auto P = std::make_shared<DCRTParams>(co0, q0, r0, device);
-        DCRTPolyHip x(P, (Format)f0, batch, Uninit{});
+        DCRTPolyHip x = result(P, (Format)f0, batch);
         x.SetValues(flat, (Format)f0);
         return x;
     }
@@ -759,13 +811,27 @@ private:
         q = get<uint64_t>(is);
         r = get<uint64_t>(is);
     }
-    // DropLastElement (dcrtpoly-impl.h:719-728): the params of the chain
-    // without its last tower (a cached plan of that basis)
-    std::shared_ptr<DCRTParams> lower_params() const {
-        if (p_->Towers() < 2) throw math_error("Removing last element of DCRTPoly object renders it invalid!");
-        std::vector<uint64_t> q(p_->Moduli().begin(), p_->Moduli().end() - 1);
-        std::vector<uint64_t> r(p_->Roots().begin(), p_->Roots().end() - 1);
-        return std::make_shared<DCRTParams>(p_->GetCyclotomicOrder(), q, r, p_->manager()->device());
+    // the element-wise family: one body per shape, the ABI function and the op's name as arguments
+    typedef int (*VvFn)(ofhe_plan_t, const uint64_t*, const uint64_t*, uint64_t*, uint32_t, void*);
+    DCRTPolyHip binary(const char* op, VvFn fn, const DCRTPolyHip& rhs, bool eval_only) const {
+        check_compat(rhs, op, eval_only);
+        DCRTPolyHip r = result(p_, f_, batch_);
+        check(fn(p_->plan(), data(), rhs.data(), r.data(), batch_, nullptr), op);
+        return r;
+    }
+    DCRTPolyHip& binary_eq(const char* op, VvFn fn, const DCRTPolyHip& rhs, bool eval_only) {
+        check_compat(rhs, op, eval_only);
+        check(fn(p_->plan(), data(), rhs.data(), data(), batch_, nullptr), op);
+        return *this;
+    }
+    void per_tower(const char* op, const char* what, const std::vector<uint64_t>& s) const {
+        if (s.size() != p_->Towers()) throw math_error(std::string(op) + ": one " + what + " per tower required");
+    }
+    DCRTPolyHip scalar(const char* op, const char* what, VvFn fn, const std::vector<uint64_t>& s) const {
+        per_tower(op, what, s);
+        DCRTPolyHip r = result(p_, f_, batch_);
+        check(fn(p_->plan(), data(), s.data(), r.data(), batch_, nullptr), op);
+        return r;
     }
 
     void check_compat(const DCRTPolyHip& rhs, const char* op, bool eval_only, bool same_format = true) const {
@@ -785,6 +851,20 @@ private:
     DeviceBuffer buf_;
 };
 
+// The two argument rules the classes below share.  check_over: x is over the
+// basis P (moduli and ring); the caller gives the words after "<op>" where they
+// differ.  check_form: x is in format f.
+inline void check_over(const DCRTPolyHip& x, const DCRTParams& P, const char* op,
+                       const char* suffix = ": the polynomial is over another basis") {
+    if (x.GetParams()->Moduli() != P.Moduli() || x.GetParams()->LogN() != P.LogN())
+        throw math_error(std::string(op) + suffix);
+}
+inline void check_form(const DCRTPolyHip& x, Format f, const char* op) {
+    if (x.GetFormat() != f)
+        throw math_error(std::string(op) + (f == Format::EVALUATION ? ": EVALUATION" : ": COEFFICIENT") +
+                         " form expected");
+}
+
 // ---------------------------------------------------------------------------
 // ApproxSwitchCRTBasis (dcrtpoly-impl.h:1034-1063): x over basis Q (params of
 // x) -> basis P (paramsP), both COEFFICIENT form.
@@ -793,63 +873,61 @@ class BaseConverter {
 public:
     BaseConverter(const DCRTParams& Q, const DCRTParams& P, const std::vector<uint64_t>& QHatInvModq,
                   const std::vector<uint64_t>& QHatModp /* [sizeQ][sizeP] */) {
+        ofhe_bconv_t h = nullptr;
         check(ofhe_hip_bconv_create(Q.manager()->ctx(), Q.LogN(), (uint32_t)Q.Towers(), (uint32_t)P.Towers(),
-                                    Q.Moduli().data(), P.Moduli().data(), QHatInvModq.data(), QHatModp.data(), &h_),
+                                    Q.Moduli().data(), P.Moduli().data(), QHatInvModq.data(), QHatModp.data(), &h),
               "BaseConverter");
+        h_.reset(h);
     }
-    ~BaseConverter() {
-        if (h_) ofhe_hip_bconv_destroy(h_);
-    }
-    BaseConverter(const BaseConverter&) = delete;
-    BaseConverter& operator=(const BaseConverter&) = delete;
     DCRTPolyHip ApproxSwitchCRTBasis(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP) const {
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("ApproxSwitchCRTBasis: COEFFICIENT form expected");
-        DCRTPolyHip out(paramsP, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_approx_switch_crt_basis(h_, x.data(), out.data(), x.Batch(), nullptr), "ApproxSwitchCRTBasis");
-        return out;
+        return switch_basis("ApproxSwitchCRTBasis", ofhe_hip_approx_switch_crt_basis, x, paramsP);
     }
     // SwitchCRTBasis (dcrtpoly-impl.h:1178-1230), the exact switch with the
     // floating-point overflow count: this converter must hold the true CRT
     // tables (QHatInvModq, QHatModp); alphaQModp and qInv are derived from its
     // moduli inside the backend.
     DCRTPolyHip SwitchCRTBasis(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP) const {
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("SwitchCRTBasis: COEFFICIENT form expected");
-        DCRTPolyHip out(paramsP, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_switch_crt_basis(h_, x.data(), out.data(), x.Batch(), nullptr), "SwitchCRTBasis");
-        return out;
+        return switch_basis("SwitchCRTBasis", ofhe_hip_switch_crt_basis, x, paramsP);
     }
 
-    ofhe_bconv_t handle() const { return h_; }
+    ofhe_bconv_t handle() const { return h_.get(); }
 
 private:
-    ofhe_bconv_t h_ = nullptr;
+    DCRTPolyHip switch_basis(const char* op, int (*fn)(ofhe_bconv_t, const uint64_t*, uint64_t*, uint32_t, void*),
+                             const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP) const {
+        check_form(x, Format::COEFFICIENT, op);
+        DCRTPolyHip out = DCRTPolyHip::result(paramsP, Format::COEFFICIENT, x.Batch());
+        check(fn(h_.get(), x.data(), out.data(), x.Batch(), nullptr), op);
+        return out;
+    }
+    Handle<ofhe_bconv_s, ofhe_hip_bconv_destroy> h_;
 };
 
-// ApproxModUp (dcrtpoly-impl.h:1085-1131): x over Q (either format) -> a
-// polynomial over paramsQP = Q|P in EVALUATION form.  q_to_p converts Q -> P.
-inline DCRTPolyHip ApproxModUp(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP,
-                               const std::shared_ptr<DCRTParams>& paramsQP, const BaseConverter& q_to_p) {
+// The body of ApproxModUp and ExpandCRTBasis: x over Q (either format) ->
+// paramsQP = Q|P in EVALUATION form through q_to_p.
+inline DCRTPolyHip mod_up(const char* op,
+                          int (*fn)(ofhe_plan_t, ofhe_plan_t, ofhe_bconv_t, int, const uint64_t*, uint64_t*, uint32_t,
+                                    void*),
+                          const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP,
+                          const std::shared_ptr<DCRTParams>& paramsQP, const BaseConverter& q_to_p) {
     const auto& Q = x.GetParams();
-    if (paramsQP->Towers() != Q->Towers() + paramsP->Towers()) throw math_error("ApproxModUp: paramsQP size");
-    DCRTPolyHip out(paramsQP, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
-    check(ofhe_hip_approx_mod_up(Q->plan(), paramsP->plan(), q_to_p.handle(), x.GetFormat() == Format::EVALUATION,
-                                 x.data(), out.data(), x.Batch(), nullptr),
-          "ApproxModUp");
+    if (paramsQP->Towers() != Q->Towers() + paramsP->Towers()) throw math_error(std::string(op) + ": paramsQP size");
+    DCRTPolyHip out = DCRTPolyHip::result(paramsQP, Format::EVALUATION, x.Batch());
+    check(fn(Q->plan(), paramsP->plan(), q_to_p.handle(), x.GetFormat() == Format::EVALUATION, x.data(), out.data(),
+             x.Batch(), nullptr),
+          op);
     return out;
 }
-
+// ApproxModUp (dcrtpoly-impl.h:1085-1131): the approximate switch; q_to_p converts Q -> P.
+inline DCRTPolyHip ApproxModUp(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP,
+                               const std::shared_ptr<DCRTParams>& paramsQP, const BaseConverter& q_to_p) {
+    return mod_up("ApproxModUp", ofhe_hip_approx_mod_up, x, paramsP, paramsQP, q_to_p);
+}
 // ExpandCRTBasis with resultFormat = EVALUATION (dcrtpoly-impl.h:1311-1358):
-// x over Q (either format) -> Q|P in EVALUATION form through the exact switch;
-// q_to_p holds the true CRT tables of Q -> P.
+// the exact switch; q_to_p holds the true CRT tables of Q -> P.
 inline DCRTPolyHip ExpandCRTBasis(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsP,
                                   const std::shared_ptr<DCRTParams>& paramsQP, const BaseConverter& q_to_p) {
-    const auto& Q = x.GetParams();
-    if (paramsQP->Towers() != Q->Towers() + paramsP->Towers()) throw math_error("ExpandCRTBasis: paramsQP size");
-    DCRTPolyHip out(paramsQP, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
-    check(ofhe_hip_expand_crt_basis(Q->plan(), paramsP->plan(), q_to_p.handle(), x.GetFormat() == Format::EVALUATION,
-                                    x.data(), out.data(), x.Batch(), nullptr),
-          "ExpandCRTBasis");
-    return out;
+    return mod_up("ExpandCRTBasis", ofhe_hip_expand_crt_basis, x, paramsP, paramsQP, q_to_p);
 }
 
 // ScaleAndRound, DCRTPoly -> DCRTPoly (dcrtpoly-impl.h:1876-1955): x over Q|P
@@ -870,29 +948,40 @@ public:
             if (row.size() != si + 1) throw math_error("ScaleAndRound: table row size");
             flat.insert(flat.end(), row.begin(), row.end());
         }
+        ofhe_scale_round_t h = nullptr;
         check(ofhe_hip_scale_round_create(Q.manager()->ctx(), Q.LogN(), (uint32_t)Q.Towers(), (uint32_t)P.Towers(),
                                           Q.Moduli().data(), P.Moduli().data(), outIsQ ? 1 : 0, flat.data(),
-                                          tOSHatInvModsDivsFrac.data(), &h_),
+                                          tOSHatInvModsDivsFrac.data(), &h),
               "ScaleAndRound");
+        h_.reset(h);
     }
-    ~ScaleAndRound() {
-        if (h_) ofhe_hip_scale_round_destroy(h_);
-    }
-    ScaleAndRound(const ScaleAndRound&) = delete;
-    ScaleAndRound& operator=(const ScaleAndRound&) = delete;
     DCRTPolyHip operator()(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsOutput) const {
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("ScaleAndRound: COEFFICIENT form expected");
-        DCRTPolyHip out(paramsOutput, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_scale_and_round(h_, x.data(), out.data(), x.Batch(), nullptr), "ScaleAndRound");
+        check_form(x, Format::COEFFICIENT, "ScaleAndRound");
+        DCRTPolyHip out = DCRTPolyHip::result(paramsOutput, Format::COEFFICIENT, x.Batch());
+        check(ofhe_hip_scale_and_round(h_.get(), x.data(), out.data(), x.Batch(), nullptr), "ScaleAndRound");
         return out;
     }
     bool OutIsQ() const { return out_is_q_; }
-    ofhe_scale_round_t handle() const { return h_; }
+    ofhe_scale_round_t handle() const { return h_.get(); }
 
 private:
-    ofhe_scale_round_t h_ = nullptr;
+    Handle<ofhe_scale_round_s, ofhe_hip_scale_round_destroy> h_;
     bool out_is_q_;
 };
+
+// What every BFV EvalMult (HPS family, BEHZ, leveled) takes and returns: four
+// EVALUATION-form operands over Q of one batch are checked, and the three
+// outputs over Q in COEFFICIENT form come back uninitialised.
+inline std::vector<DCRTPolyHip> bfv_mult_outputs(const char* op, const std::shared_ptr<DCRTParams>& Q,
+                                                 const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
+                                                 const DCRTPolyHip& d1) {
+    for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
+        if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q->Moduli() || v->Batch() != c0.Batch())
+            throw math_error(std::string(op) + ": EVALUATION-form ciphertexts over Q of one batch expected");
+    std::vector<DCRTPolyHip> out;
+    for (int k = 0; k < 3; k++) out.push_back(DCRTPolyHip::result(Q, Format::COEFFICIENT, c0.Batch()));
+    return out;
+}
 
 // LeveledSHEBFVRNS::EvalMult (bfvrns-leveledshe.cpp:168-408), HPS or HPSPOVERQ,
 // for two 2-element ciphertexts, from the outputs of the reference's getters
@@ -912,26 +1001,18 @@ public:
           r_to_q_(*R_, *Q_, RHatInvModr, RHatModq),
           sr_(*Q_, *R_, tech == HPSPOVERQ, tSHatInvModsDivsModo, tSHatInvModsDivsFrac) {
         if (tech == HPSPOVERQ) neg_.reset(new BaseConverter(*Q_, *R_, mNegRlQHatInvModq, qInvModr));
+        ofhe_bfv_mult_t h = nullptr;
         check(ofhe_hip_bfv_mult_create(Q_->manager()->ctx(), (int)tech, Q_->plan(), R_->plan(), QR_->plan(),
                                        q_to_r_.handle(), r_to_q_.handle(), neg_ ? neg_->handle() : nullptr,
-                                       sr_.handle(), &h_),
+                                       sr_.handle(), &h),
               "BfvMult");
+        h_.reset(h);
     }
-    ~BfvMult() {
-        if (h_) ofhe_hip_bfv_mult_destroy(h_);
-    }
-    BfvMult(const BfvMult&) = delete;
-    BfvMult& operator=(const BfvMult&) = delete;
     // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
     std::vector<DCRTPolyHip> EvalMult(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
                                       const DCRTPolyHip& d1) const {
-        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
-            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
-                v->Batch() != c0.Batch())
-                throw math_error("BfvMult::EvalMult: EVALUATION-form ciphertexts over Q of one batch expected");
-        std::vector<DCRTPolyHip> out;
-        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_bfv_eval_mult(h_, c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(), out[1].data(),
+        auto out = bfv_mult_outputs("BfvMult::EvalMult", Q_, c0, c1, d0, d1);
+        check(ofhe_hip_bfv_eval_mult(h_.get(), c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(), out[1].data(),
                                      out[2].data(), c0.Batch(), nullptr),
               "BfvMult::EvalMult");
         return out;
@@ -940,14 +1021,14 @@ public:
     const BaseConverter& RToQ() const { return r_to_q_; }
     const BaseConverter* QToRNeg() const { return neg_.get(); }  // null for HPS
     const ScaleAndRound& Scale() const { return sr_; }
-    ofhe_bfv_mult_t handle() const { return h_; }
+    ofhe_bfv_mult_t handle() const { return h_.get(); }
 
 private:
     std::shared_ptr<DCRTParams> Q_, R_, QR_;
     BaseConverter q_to_r_, r_to_q_;
     ScaleAndRound sr_;
     std::unique_ptr<BaseConverter> neg_;
-    ofhe_bfv_mult_t h_ = nullptr;
+    Handle<ofhe_bfv_mult_s, ofhe_hip_bfv_mult_destroy> h_;
 };
 
 // The BEHZ tables as the reference's getters return them
@@ -987,61 +1068,52 @@ public:
                                   T.QModbsk.data(),      T.mtildeInvModbsk.data(),   T.tQInvModbsk.data(),
                                   T.BHatInvModb.data(),  T.BHatModq.data(),    T.BHatModmsk.data(),
                                   &T.BInvModmsk,         T.BModq.data()};
+        ofhe_behz_t h = nullptr;
         check(ofhe_hip_behz_create(Q_->manager()->ctx(), Q_->LogN(), (uint32_t)sq, Q_->Moduli().data(), (uint32_t)sb,
-                                   Bsk_->Moduli().data(), t, &tb, &h_),
+                                   Bsk_->Moduli().data(), t, &tb, &h),
               "BehzBasis");
+        h_.reset(h);
     }
-    ~BehzBasis() {
-        if (h_) ofhe_hip_behz_destroy(h_);
-    }
-    BehzBasis(const BehzBasis&) = delete;
-    BehzBasis& operator=(const BehzBasis&) = delete;
 
     DCRTPolyHip FastBaseConvqToBskMontgomery(const DCRTPolyHip& x) const {
-        over(x, *Q_, "FastBaseConvqToBskMontgomery");
-        DCRTPolyHip out(QBsk_, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_behz_expand(h_, Q_->plan(), Bsk_->plan(), x.GetFormat() == Format::EVALUATION, x.data(),
+        check_over(x, *Q_, "FastBaseConvqToBskMontgomery");
+        DCRTPolyHip out = DCRTPolyHip::result(QBsk_, Format::EVALUATION, x.Batch());
+        check(ofhe_hip_behz_expand(h_.get(), Q_->plan(), Bsk_->plan(), x.GetFormat() == Format::EVALUATION, x.data(),
                                    out.data(), x.Batch(), nullptr),
               "FastBaseConvqToBskMontgomery");
         return out;
     }
     DCRTPolyHip FastRNSFloorq(const DCRTPolyHip& x) const {
-        over(x, *QBsk_, "FastRNSFloorq");
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("FastRNSFloorq: COEFFICIENT form expected");
-        DCRTPolyHip out(Bsk_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_behz_floor(h_, x.data(), out.data(), x.Batch(), nullptr), "FastRNSFloorq");
-        return out;
+        return coeff_step("FastRNSFloorq", ofhe_hip_behz_floor, x, QBsk_, Bsk_);
     }
     DCRTPolyHip FastBaseConvSK(const DCRTPolyHip& x) const {
-        over(x, *Bsk_, "FastBaseConvSK");
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("FastBaseConvSK: COEFFICIENT form expected");
-        DCRTPolyHip out(Q_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_behz_conv_sk(h_, x.data(), out.data(), x.Batch(), nullptr), "FastBaseConvSK");
-        return out;
+        return coeff_step("FastBaseConvSK", ofhe_hip_behz_conv_sk, x, Bsk_, Q_);
     }
     // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
     std::vector<DCRTPolyHip> BfvMultBehz(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
                                          const DCRTPolyHip& d1) const {
-        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
-            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
-                v->Batch() != c0.Batch())
-                throw math_error("BfvMultBehz: EVALUATION-form ciphertexts over Q of one batch expected");
-        std::vector<DCRTPolyHip> out;
-        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_bfv_eval_mult_behz(h_, Q_->plan(), Bsk_->plan(), QBsk_->plan(), c0.data(), c1.data(), d0.data(),
-                                          d1.data(), out[0].data(), out[1].data(), out[2].data(), c0.Batch(), nullptr),
+        auto out = bfv_mult_outputs("BfvMultBehz", Q_, c0, c1, d0, d1);
+        check(ofhe_hip_bfv_eval_mult_behz(h_.get(), Q_->plan(), Bsk_->plan(), QBsk_->plan(), c0.data(), c1.data(),
+                                          d0.data(), d1.data(), out[0].data(), out[1].data(), out[2].data(), c0.Batch(),
+                                          nullptr),
               "BfvMultBehz");
         return out;
     }
-    ofhe_behz_t handle() const { return h_; }
+    ofhe_behz_t handle() const { return h_.get(); }
 
 private:
-    static void over(const DCRTPolyHip& x, const DCRTParams& P, const char* what) {
-        if (x.GetParams()->Moduli() != P.Moduli() || x.GetParams()->LogN() != P.LogN())
-            throw math_error(std::string(what) + ": the polynomial is over another basis");
+    // FastRNSFloorq and FastBaseConvSK: x over `from` in COEFFICIENT form -> `to`, COEFFICIENT
+    DCRTPolyHip coeff_step(const char* op, int (*fn)(ofhe_behz_t, const uint64_t*, uint64_t*, uint32_t, void*),
+                           const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& from,
+                           const std::shared_ptr<DCRTParams>& to) const {
+        check_over(x, *from, op);
+        check_form(x, Format::COEFFICIENT, op);
+        DCRTPolyHip out = DCRTPolyHip::result(to, Format::COEFFICIENT, x.Batch());
+        check(fn(h_.get(), x.data(), out.data(), x.Batch(), nullptr), op);
+        return out;
     }
     std::shared_ptr<DCRTParams> Q_, Bsk_, QBsk_;
-    ofhe_behz_t h_ = nullptr;
+    Handle<ofhe_behz_s, ofhe_hip_behz_destroy> h_;
 };
 
 // The decryption tables as the reference's getters return them
@@ -1077,66 +1149,58 @@ public:
                                          ptr(T.tQHatInvModqDivqFrac), ptr(T.tQHatInvModqBDivqFrac),
                                          ptr(T.tgammaQHatInvModq),    ptr(T.negInvqModtgamma),
                                          ptr(T.tInvModq),             T.tInvModq.empty() ? nullptr : &T.negQModt};
+        ofhe_bfv_decrypt_t h = nullptr;
         check(ofhe_hip_bfv_decrypt_create(Q_->manager()->ctx(), Q_->LogN(), (uint32_t)sq, Q_->Moduli().data(), t,
-                                          technique, &tb, &h_),
+                                          technique, &tb, &h),
               "BfvDecrypt");
+        h_.reset(h);
     }
-    ~BfvDecrypt() {
-        if (h_) ofhe_hip_bfv_decrypt_destroy(h_);
-    }
-    BfvDecrypt(const BfvDecrypt&) = delete;
-    BfvDecrypt& operator=(const BfvDecrypt&) = delete;
 
     // the loop that runs: 0..7 for A..H, OFHE_BFV_DECRYPT_BEHZ, OFHE_BFV_DECRYPT_ONE_TOWER
     int Branch() const {
         int b = -1;
-        check(ofhe_hip_bfv_decrypt_branch(h_, &b), "BfvDecrypt::Branch");
+        check(ofhe_hip_bfv_decrypt_branch(h_.get(), &b), "BfvDecrypt::Branch");
         return b;
     }
     std::vector<uint64_t> ScaleAndRound(const DCRTPolyHip& x) const {
-        over(x, "ScaleAndRound");
-        if (x.GetFormat() != Format::COEFFICIENT) throw math_error("ScaleAndRound: COEFFICIENT form expected");
+        check_over(x, *Q_, "ScaleAndRound");
+        check_form(x, Format::COEFFICIENT, "ScaleAndRound");
         DeviceBuffer out(Q_->manager(), (size_t)x.Batch() * Q_->GetRingDimension());
-        check(ofhe_hip_bfv_decrypt_scale_round(h_, x.data(), out.get(), x.Batch(), nullptr), "ScaleAndRound");
+        check(ofhe_hip_bfv_decrypt_scale_round(h_.get(), x.data(), out.get(), x.Batch(), nullptr), "ScaleAndRound");
         return fetch(out);
     }
     std::vector<uint64_t> Decrypt(const std::vector<DCRTPolyHip>& cv, const DCRTPolyHip& s) const {
         if (cv.size() != 2 && cv.size() != 3) throw math_error("Decrypt: 2 or 3 ciphertext elements expected");
         for (const auto& c : cv) {
-            over(c, "Decrypt");
+            check_over(c, *Q_, "Decrypt");
             if (c.GetFormat() != cv[0].GetFormat() || c.Batch() != cv[0].Batch())
                 throw math_error("Decrypt: elements of one format and one batch expected");
         }
-        over(s, "Decrypt");
+        check_over(s, *Q_, "Decrypt");
         if (s.GetFormat() != Format::EVALUATION || s.Batch() != 1)
             throw math_error("Decrypt: the secret key in EVALUATION form, batch 1, expected");
         DeviceBuffer out(Q_->manager(), (size_t)cv[0].Batch() * Q_->GetRingDimension());
-        check(ofhe_hip_bfv_decrypt(h_, Q_->plan(), (uint32_t)cv.size(), cv[0].GetFormat() == Format::EVALUATION,
+        check(ofhe_hip_bfv_decrypt(h_.get(), Q_->plan(), (uint32_t)cv.size(), cv[0].GetFormat() == Format::EVALUATION,
                                    cv[0].data(), cv[1].data(), cv.size() == 3 ? cv[2].data() : nullptr, s.data(),
                                    out.get(), cv[0].Batch(), nullptr),
               "Decrypt");
         return fetch(out);
     }
     const std::shared_ptr<DCRTParams>& GetParams() const { return Q_; }
-    ofhe_bfv_decrypt_t handle() const { return h_; }
+    ofhe_bfv_decrypt_t handle() const { return h_.get(); }
 
 private:
-    void over(const DCRTPolyHip& x, const char* what) const {
-        if (x.GetParams()->Moduli() != Q_->Moduli() || x.GetParams()->LogN() != Q_->LogN())
-            throw math_error(std::string(what) + ": the polynomial is over another basis");
-    }
     static std::vector<uint64_t> fetch(const DeviceBuffer& d) {
         std::vector<uint64_t> h(d.size());
         d.download(h.data());
         return h;
     }
     std::shared_ptr<DCRTParams> Q_;
-    ofhe_bfv_decrypt_t h_ = nullptr;
+    Handle<ofhe_bfv_decrypt_s, ofhe_hip_bfv_decrypt_destroy> h_;
 };
 
 inline void DCRTPolyHip::TimesQovert(const BfvDecrypt& d) {
-    if (p_->Moduli() != d.GetParams()->Moduli() || p_->LogN() != d.GetParams()->LogN())
-        throw math_error("TimesQovert: the polynomial is over another basis");
+    check_over(*this, *d.GetParams(), "TimesQovert");
     check(ofhe_hip_times_q_over_t(d.handle(), data(), data(), batch_, nullptr), "TimesQovert");
 }
 
@@ -1144,11 +1208,11 @@ inline void DCRTPolyHip::TimesQovert(const BfvDecrypt& d) {
 inline DCRTPolyHip ApproxModDown(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsQ,
                                  const std::shared_ptr<DCRTParams>& paramsP, const BaseConverter& p_to_q,
                                  const std::vector<uint64_t>& PInvModq, uint64_t t = 0) {
-    if (x.GetFormat() != Format::EVALUATION) throw math_error("ApproxModDown: EVALUATION form expected");
+    check_form(x, Format::EVALUATION, "ApproxModDown");
     if (x.GetParams()->Towers() != paramsQ->Towers() + paramsP->Towers())
         throw math_error("ApproxModDown: tower count mismatch");
     if (PInvModq.size() != paramsQ->Towers()) throw math_error("ApproxModDown: PInvModq size");
-    DCRTPolyHip out(paramsQ, Format::EVALUATION, x.Batch(), DCRTPolyHip::Uninit{});
+    DCRTPolyHip out = DCRTPolyHip::result(paramsQ, Format::EVALUATION, x.Batch());
     check(ofhe_hip_approx_mod_down(paramsQ->plan(), paramsP->plan(), p_to_q.handle(), PInvModq.data(), t, x.data(),
                                    out.data(), x.Batch(), nullptr),
           "ApproxModDown");
@@ -1162,36 +1226,30 @@ inline DCRTPolyHip ApproxModDown(const DCRTPolyHip& x, const std::shared_ptr<DCR
 class KeySwitchHybrid {
 public:
     KeySwitchHybrid(const DCRTParams& Q, const DCRTParams& P, uint32_t numPartQ) {
+        ofhe_ks_t h = nullptr;
         check(ofhe_hip_ks_create(Q.manager()->ctx(), Q.LogN(), (uint32_t)Q.Towers(), Q.Moduli().data(),
                                  Q.Roots().data(), (uint32_t)P.Towers(), P.Moduli().data(), P.Roots().data(), numPartQ,
-                                 &h_),
+                                 &h),
               "KeySwitchHybrid");
+        h_.reset(h);
         sizeQ_ = Q.Towers();
         sizeP_ = P.Towers();
         numPartQ_ = numPartQ;
     }
-    ~KeySwitchHybrid() {
-        if (h_) ofhe_hip_ks_destroy(h_);
-    }
-    KeySwitchHybrid(const KeySwitchHybrid&) = delete;
-    KeySwitchHybrid& operator=(const KeySwitchHybrid&) = delete;
 
     // KeySwitchCore(a, evalKey) (keyswitch-hybrid.cpp:325-328): c is over Ql
     // (its params give the level), EVALUATION form.  t > 0 for BGV.
     std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchCore(const DCRTPolyHip& c, const DCRTPolyHip& key_b,
                                                       const DCRTPolyHip& key_a, uint64_t t = 0) const {
-        if (c.GetFormat() != Format::EVALUATION) throw math_error("KeySwitchCore: EVALUATION form expected");
+        check_form(c, Format::EVALUATION, "KeySwitchCore");
         const uint32_t l = (uint32_t)c.GetParams()->Towers();
         if (l > sizeQ_) throw math_error("KeySwitchCore: ciphertext has more towers than Q");
-        if (key_b.Batch() != numPartQ_ || key_a.Batch() != numPartQ_ ||
-            key_b.GetParams()->Towers() != sizeQ_ + sizeP_ || key_a.GetParams()->Towers() != sizeQ_ + sizeP_)
-            throw math_error("KeySwitchCore: evaluation key must be numPartQ polynomials over Q|P");
-        DCRTPolyHip o0(c.GetParams(), Format::EVALUATION, c.Batch(), DCRTPolyHip::Uninit{}),
-            o1(c.GetParams(), Format::EVALUATION, c.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_core(h_, l, c.data(), key_b.data(), key_a.data(), o0.data(), o1.data(), t, c.Batch(),
-                               nullptr),
+        check_key("KeySwitchCore", &key_b, &key_a);
+        auto o = DCRTPolyHip::result_pair(c.GetParams(), Format::EVALUATION, c.Batch());
+        check(ofhe_hip_ks_core(h_.get(), l, c.data(), key_b.data(), key_a.data(), o.first.data(), o.second.data(), t,
+                               c.Batch(), nullptr),
               "KeySwitchCore");
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
 
     // one relinearisation key: the b and a polynomials, as KeySwitchCore takes them
@@ -1222,20 +1280,16 @@ public:
         if (cv.size() < 3) throw math_error("Relinearize: 3 or more ciphertext elements expected");
         if (keys.size() + 2 != cv.size()) throw math_error("Relinearize: one evaluation key per element past the second");
         const uint32_t l = she_level("Relinearize", cv);
-        std::vector<const uint64_t*> c, kb, ka;
+        std::vector<const uint64_t*> c;
         for (const DCRTPolyHip* e : cv) c.push_back(e->data());
-        for (const RelinKey& k : keys) {
-            check_key("Relinearize", *k.first, *k.second);
-            kb.push_back(k.first->data());
-            ka.push_back(k.second->data());
-        }
+        for (const RelinKey& k : keys) check_key("Relinearize", k.first, k.second);
+        const KeyPtrs k = key_ptrs(keys);
         const DCRTPolyHip& f = *cv[0];
-        DCRTPolyHip o0(f.GetParams(), Format::EVALUATION, f.Batch(), DCRTPolyHip::Uninit{}),
-            o1(f.GetParams(), Format::EVALUATION, f.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_relinearize(h_, l, (uint32_t)cv.size(), c.data(), kb.data(), ka.data(), o0.data(), o1.data(),
-                                      t, f.Batch(), nullptr),
+        auto o = DCRTPolyHip::result_pair(f.GetParams(), Format::EVALUATION, f.Batch());
+        check(ofhe_hip_ks_relinearize(h_.get(), l, (uint32_t)cv.size(), c.data(), k.b.data(), k.a.data(),
+                                      o.first.data(), o.second.data(), t, f.Batch(), nullptr),
               "Relinearize");
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
     // ModReduceInternalInPlace (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77) of every
     // element of cv: `levels` >= 1 towers dropped, the results over the lowered params
@@ -1249,12 +1303,12 @@ public:
         std::vector<const uint64_t*> x;
         std::vector<uint64_t*> o;
         for (const DCRTPolyHip* e : cv) {
-            out.emplace_back(lp, Format::EVALUATION, e->Batch(), DCRTPolyHip::Uninit{});
+            out.push_back(DCRTPolyHip::result(lp, Format::EVALUATION, e->Batch()));
             x.push_back(e->data());
         }
         for (DCRTPolyHip& r : out) o.push_back(r.data());
-        check(ofhe_hip_ks_rescale(h_, l, scheme, t, levels, (uint32_t)cv.size(), x.data(), o.data(), cv[0]->Batch(),
-                                  nullptr),
+        check(ofhe_hip_ks_rescale(h_.get(), l, scheme, t, levels, (uint32_t)cv.size(), x.data(), o.data(),
+                                  cv[0]->Batch(), nullptr),
               "Rescale");
         return out;
     }
@@ -1271,18 +1325,17 @@ public:
 
     // LeveledSHEBase::EvalFastRotationPrecompute (base-leveledshe.cpp:462-469)
     HoistedDigits FastRotationPrecompute(const DCRTPolyHip& c1) const {
-        if (c1.GetFormat() != Format::EVALUATION)
-            throw math_error("FastRotationPrecompute: EVALUATION form expected");
+        check_form(c1, Format::EVALUATION, "FastRotationPrecompute");
         const uint32_t l = (uint32_t)c1.GetParams()->Towers();
         if (l > sizeQ_) throw math_error("FastRotationPrecompute: ciphertext has more towers than Q");
         uint32_t beta = 0;
-        check(ofhe_hip_ks_digits(h_, l, nullptr, &beta), "FastRotationPrecompute");
+        check(ofhe_hip_ks_digits(h_.get(), l, nullptr, &beta), "FastRotationPrecompute");
         HoistedDigits d;
         d.buf = DeviceBuffer(c1.GetParams()->manager(),
                              (size_t)c1.Batch() * beta * (l + sizeP_) * c1.GetParams()->GetRingDimension());
         d.size_ql = l;
         d.batch = c1.Batch();
-        check(ofhe_hip_ks_precompute(h_, l, c1.data(), d.buf.get(), d.batch, nullptr), "FastRotationPrecompute");
+        check(ofhe_hip_ks_precompute(h_.get(), l, c1.data(), d.buf.get(), d.batch, nullptr), "FastRotationPrecompute");
         return d;
     }
 
@@ -1294,7 +1347,7 @@ public:
         if (c0.GetParams()->Towers() != digits.size_ql)
             throw math_error("FastRotation: c0 and the digits are at different levels");
         return rot_run(c0.GetParams(), digits, autoIndex, keys, [&](const KeyPtrs& k, uint64_t* o0, uint64_t* o1) {
-            check(ofhe_hip_ks_fast_rotation(h_, digits.size_ql, digits.buf.get(), c0.data(),
+            check(ofhe_hip_ks_fast_rotation(h_.get(), digits.size_ql, digits.buf.get(), c0.data(),
                                             (uint32_t)autoIndex.size(), autoIndex.data(), k.b.data(), k.a.data(), o0,
                                             o1, t, digits.batch, nullptr),
                   "FastRotation");
@@ -1312,7 +1365,7 @@ public:
         if (!paramsQlP || paramsQlP->Towers() != digits.size_ql + sizeP_)
             throw math_error("FastRotationExt: paramsQlP must have the level's towers plus P");
         return rot_run(paramsQlP, digits, autoIndex, keys, [&](const KeyPtrs& k, uint64_t* o0, uint64_t* o1) {
-            check(ofhe_hip_ks_fast_rotation_ext(h_, digits.size_ql, digits.buf.get(), c0 ? c0->data() : nullptr,
+            check(ofhe_hip_ks_fast_rotation_ext(h_.get(), digits.size_ql, digits.buf.get(), c0 ? c0->data() : nullptr,
                                                 (uint32_t)autoIndex.size(), autoIndex.data(), k.b.data(),
                                                 k.a.data(), o0, o1, digits.batch, nullptr),
                   "FastRotationExt");
@@ -1326,11 +1379,11 @@ public:
     // KeySwitchHYBRID::KeySwitchExt (keyswitch-hybrid.cpp:231-256) on one
     // element: c over Ql -> c * PModq on the Q towers of paramsQlP, zero on P.
     DCRTPolyHip KeySwitchExt(const DCRTPolyHip& c, const std::shared_ptr<DCRTParams>& paramsQlP) const {
-        if (c.GetFormat() != Format::EVALUATION) throw math_error("KeySwitchExt: EVALUATION form expected");
+        check_form(c, Format::EVALUATION, "KeySwitchExt");
         const uint32_t l = (uint32_t)c.GetParams()->Towers();
         ext_params("KeySwitchExt", paramsQlP, l);
-        DCRTPolyHip out(paramsQlP, Format::EVALUATION, c.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_ext(h_, l, c.data(), out.data(), c.Batch(), nullptr), "KeySwitchExt");
+        DCRTPolyHip out = DCRTPolyHip::result(paramsQlP, Format::EVALUATION, c.Batch());
+        check(ofhe_hip_ks_ext(h_.get(), l, c.data(), out.data(), c.Batch(), nullptr), "KeySwitchExt");
         return out;
     }
 
@@ -1342,9 +1395,7 @@ public:
                                                    const DCRTPolyHip& diag, const std::vector<uint8_t>& present,
                                                    uint32_t nsum) const {
         const auto& op = x0.GetParams();
-        if (x0.GetFormat() != Format::EVALUATION || x1.GetFormat() != Format::EVALUATION ||
-            diag.GetFormat() != Format::EVALUATION)
-            throw math_error("MultExtSum: EVALUATION form expected");
+        for (const DCRTPolyHip* v : {&x0, &x1, &diag}) check_form(*v, Format::EVALUATION, "MultExtSum");
         if (op->Towers() <= sizeP_ || x1.GetParams()->Moduli() != op->Moduli() ||
             diag.GetParams()->Moduli() != op->Moduli())
             throw math_error("MultExtSum: the terms and the diagonals must be over one Ql|P basis");
@@ -1354,13 +1405,12 @@ public:
             throw math_error("MultExtSum: one presence byte per diagonal required");
         const uint32_t batch = x0.Batch() / nterm, l = (uint32_t)(op->Towers() - sizeP_);
         const uint64_t poly = (uint64_t)op->Towers() * op->GetRingDimension();
-        DCRTPolyHip o0(op, Format::EVALUATION, nsum * batch, DCRTPolyHip::Uninit{}),
-            o1(op, Format::EVALUATION, nsum * batch, DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_mult_ext_sum(h_, l, nterm, x0.data(), x1.data(), batch * poly, diag.data(), poly,
-                                       present.empty() ? nullptr : present.data(), nsum, o0.data(), o1.data(), batch,
-                                       nullptr),
+        auto o = DCRTPolyHip::result_pair(op, Format::EVALUATION, nsum * batch);
+        check(ofhe_hip_ks_mult_ext_sum(h_.get(), l, nterm, x0.data(), x1.data(), batch * poly, diag.data(), poly,
+                                       present.empty() ? nullptr : present.data(), nsum, o.first.data(),
+                                       o.second.data(), batch, nullptr),
               "MultExtSum");
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
 
     // Sum over the digit sets of EvalFastRotationExt(., autoIndex[j], digits_j, false)
@@ -1380,19 +1430,14 @@ public:
         if (addend1 && (addend1->GetFormat() != Format::EVALUATION || addend1->Batch() % batch ||
                         addend1->GetParams()->Moduli() != paramsQlP->Moduli()))
             throw math_error("FastRotationExtSum: addend1 must be nadd * batch EVALUATION polynomials over Ql|P");
-        KeyPtrs k;
-        for (const auto& key : keys) {
-            k.b.push_back(key.first->data());
-            k.a.push_back(key.second->data());
-        }
-        DCRTPolyHip o0(paramsQlP, Format::EVALUATION, batch, DCRTPolyHip::Uninit{}),
-            o1(paramsQlP, Format::EVALUATION, batch, DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_fast_rotation_ext_sum(h_, digits.size_ql, nset, digits.buf.get(), autoIndex.data(),
+        const KeyPtrs k = key_ptrs(keys);
+        auto o = DCRTPolyHip::result_pair(paramsQlP, Format::EVALUATION, batch);
+        check(ofhe_hip_ks_fast_rotation_ext_sum(h_.get(), digits.size_ql, nset, digits.buf.get(), autoIndex.data(),
                                                 k.b.data(), k.a.data(), addend1 ? addend1->data() : nullptr,
-                                                addend1 ? addend1->Batch() / batch : 0, o0.data(), o1.data(), batch,
-                                                nullptr),
+                                                addend1 ? addend1->Batch() / batch : 0, o.first.data(),
+                                                o.second.data(), batch, nullptr),
               "FastRotationExtSum");
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
 
     // One BSGS level: indices, key ids and presence.  An index = 1 mod 2N is
@@ -1409,7 +1454,7 @@ public:
                                                         const BsgsPlan& plan, const DCRTPolyHip& diag,
                                                         uint64_t t = 0) const;
 
-    ofhe_ks_t handle() const { return h_; }
+    ofhe_ks_t handle() const { return h_.get(); }
 
 private:
     void ext_params(const char* op, const std::shared_ptr<DCRTParams>& paramsQlP, size_t l) const {
@@ -1417,21 +1462,30 @@ private:
         if (!paramsQlP || paramsQlP->Towers() != l + sizeP_)
             throw math_error(std::string(op) + ": paramsQlP must have the level's towers plus P");
     }
+    // The evaluation-key rule, known here alone: numPartQ polynomials over Q|P each
+    void check_key(const char* op, const DCRTPolyHip* key_b, const DCRTPolyHip* key_a) const {
+        if (!key_b || !key_a || key_b->Batch() != numPartQ_ || key_a->Batch() != numPartQ_ ||
+            key_b->GetParams()->Towers() != sizeQ_ + sizeP_ || key_a->GetParams()->Towers() != sizeQ_ + sizeP_)
+            throw math_error(std::string(op) + ": evaluation key must be numPartQ polynomials over Q|P");
+    }
+    // The (b, a) pointer lists the C ABI takes, from a list of keys; a NULL pair (an identity step) stays NULL
     struct KeyPtrs {
         std::vector<const uint64_t*> b, a;
     };
-    // the checks KeySwitchCore makes, for the multiplication family
-    void check_key(const char* op, const DCRTPolyHip& key_b, const DCRTPolyHip& key_a) const {
-        if (key_b.Batch() != numPartQ_ || key_a.Batch() != numPartQ_ ||
-            key_b.GetParams()->Towers() != sizeQ_ + sizeP_ || key_a.GetParams()->Towers() != sizeQ_ + sizeP_)
-            throw math_error(std::string(op) + ": evaluation key must be numPartQ polynomials over Q|P");
+    static KeyPtrs key_ptrs(const std::vector<RotationKey>& keys) {
+        KeyPtrs k;
+        for (const auto& key : keys) {
+            k.b.push_back(key.first ? key.first->data() : nullptr);
+            k.a.push_back(key.second ? key.second->data() : nullptr);
+        }
+        return k;
     }
     // every element in EVALUATION form, over one basis of at most Q's towers, of one batch: the level
     uint32_t she_level(const char* op, const std::vector<const DCRTPolyHip*>& cv) const {
         const std::string w(op);
         for (const DCRTPolyHip* e : cv) {
             if (!e) throw math_error(w + ": NULL ciphertext element");
-            if (e->GetFormat() != Format::EVALUATION) throw math_error(w + ": EVALUATION form expected");
+            check_form(*e, Format::EVALUATION, op);
             if (e->GetParams()->Moduli() != cv[0]->GetParams()->Moduli() || e->Batch() != cv[0]->Batch())
                 throw math_error(w + ": elements over one basis and of one batch expected");
         }
@@ -1439,70 +1493,54 @@ private:
         if (l > sizeQ_) throw math_error(w + ": ciphertext has more towers than Q");
         return (uint32_t)l;
     }
-    // DropLastElement `levels` times (dcrtpoly-impl.h:719-728): the params of the shorter chain
-    static std::shared_ptr<DCRTParams> lowered(const DCRTParams& p, uint32_t levels) {
-        if (levels >= p.Towers()) throw math_error("Removing last element of DCRTPoly object renders it invalid!");
-        std::vector<uint64_t> q(p.Moduli().begin(), p.Moduli().end() - levels);
-        std::vector<uint64_t> r(p.Roots().begin(), p.Roots().end() - levels);
-        return std::make_shared<DCRTParams>(p.GetCyclotomicOrder(), q, r, p.manager()->device());
-    }
     std::pair<DCRTPolyHip, DCRTPolyHip> mult(const char* op, const DCRTPolyHip& c0, const DCRTPolyHip& c1,
                                              const DCRTPolyHip* d0, const DCRTPolyHip* d1, const DCRTPolyHip& key_b,
                                              const DCRTPolyHip& key_a, int scheme, uint64_t t, uint32_t levels) const {
         std::vector<const DCRTPolyHip*> cv{&c0, &c1};
         if (d0) cv.insert(cv.end(), {d0, d1});
         const uint32_t l = she_level(op, cv);
-        check_key(op, key_b, key_a);
+        check_key(op, &key_b, &key_a);
         if (levels >= l) throw math_error(std::string(op) + ": levels must be below the towers of the operands");
         auto lp = levels ? lowered(*c0.GetParams(), levels) : c0.GetParams();
-        DCRTPolyHip o0(lp, Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{}),
-            o1(lp, Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_ks_eval_mult(h_, l, c0.data(), c1.data(), d0 ? d0->data() : nullptr, d1 ? d1->data() : nullptr,
-                                    key_b.data(), key_a.data(), scheme, t, levels, o0.data(), o1.data(), c0.Batch(),
-                                    nullptr),
+        auto o = DCRTPolyHip::result_pair(lp, Format::EVALUATION, c0.Batch());
+        check(ofhe_hip_ks_eval_mult(h_.get(), l, c0.data(), c1.data(), d0 ? d0->data() : nullptr,
+                                    d1 ? d1->data() : nullptr, key_b.data(), key_a.data(), scheme, t, levels,
+                                    o.first.data(), o.second.data(), c0.Batch(), nullptr),
               op);
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
     void rot_check(const char* op, const DCRTPolyHip* c0, const HoistedDigits& digits,
                    const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys) const {
         const std::string w(op);
         if (!digits.buf.get() || !digits.size_ql) throw math_error(w + ": empty digits");
-        if (c0 && c0->GetFormat() != Format::EVALUATION) throw math_error(w + ": EVALUATION form expected");
+        if (c0) check_form(*c0, Format::EVALUATION, op);
         if (c0 && c0->Batch() != digits.batch) throw math_error(w + ": batch mismatch");
         if (autoIndex.empty() || autoIndex.size() != keys.size())
             throw math_error(w + ": one evaluation key per automorphism index required");
-        for (const auto& k : keys)
-            if (!k.first || !k.second || k.first->Batch() != numPartQ_ || k.second->Batch() != numPartQ_ ||
-                k.first->GetParams()->Towers() != sizeQ_ + sizeP_ || k.second->GetParams()->Towers() != sizeQ_ + sizeP_)
-                throw math_error(w + ": evaluation key must be numPartQ polynomials over Q|P");
+        for (const auto& k : keys) check_key(op, k.first, k.second);
     }
     // The C ABI writes [nrot][batch][towers][N]; every rotation gets a
     // DCRTPolyHip of its own, filled by one device copy.
     template <class F>
     Rotations rot_run(const std::shared_ptr<DCRTParams>& op, const HoistedDigits& digits,
                       const std::vector<uint32_t>& autoIndex, const std::vector<RotationKey>& keys, F call) const {
-        KeyPtrs k;
-        for (const auto& key : keys) {
-            k.b.push_back(key.first->data());
-            k.a.push_back(key.second->data());
-        }
+        const KeyPtrs k = key_ptrs(keys);
         const size_t per = (size_t)digits.batch * op->Towers() * op->GetRingDimension(), nrot = autoIndex.size();
         DeviceBuffer all0(op->manager(), nrot * per), all1(op->manager(), nrot * per);
         call(k, all0.get(), all1.get());
         Rotations out;
         for (size_t r = 0; r < nrot; r++) {
-            DCRTPolyHip o0(op, Format::EVALUATION, digits.batch, DCRTPolyHip::Uninit{}),
-                o1(op, Format::EVALUATION, digits.batch, DCRTPolyHip::Uninit{});
-            check(ofhe_hip_copy_device(op->manager()->ctx(), o0.data(), all0.get() + r * per, per * 8, nullptr),
+            auto o = DCRTPolyHip::result_pair(op, Format::EVALUATION, digits.batch);
+            check(ofhe_hip_copy_device(op->manager()->ctx(), o.first.data(), all0.get() + r * per, per * 8, nullptr),
                   "FastRotation");
-            check(ofhe_hip_copy_device(op->manager()->ctx(), o1.data(), all1.get() + r * per, per * 8, nullptr),
+            check(ofhe_hip_copy_device(op->manager()->ctx(), o.second.data(), all1.get() + r * per, per * 8, nullptr),
                   "FastRotation");
-            out.emplace_back(std::move(o0), std::move(o1));
+            out.push_back(std::move(o));
         }
         return out;
     }
 
-    ofhe_ks_t h_ = nullptr;
+    Handle<ofhe_ks_s, ofhe_hip_ks_destroy> h_;
     size_t sizeQ_ = 0, sizeP_ = 0;
     uint32_t numPartQ_ = 0;
 };
@@ -1513,15 +1551,11 @@ private:
 class KsCache {
 public:
     static std::shared_ptr<KeySwitchHybrid> get(const DCRTParams& Q, const DCRTParams& P, uint32_t numPartQ) {
-        static std::mutex mu;
-        static std::map<std::vector<uint64_t>, std::shared_ptr<KeySwitchHybrid>> cache;
         std::vector<uint64_t> key{(uint64_t)Q.manager()->device(), Q.LogN(), numPartQ, Q.Towers()};
         key.insert(key.end(), Q.Moduli().begin(), Q.Moduli().end());
         key.insert(key.end(), P.Moduli().begin(), P.Moduli().end());
-        std::lock_guard<std::mutex> lk(mu);
-        auto& e = cache[key];
-        if (!e) e = std::make_shared<KeySwitchHybrid>(Q, P, numPartQ);
-        return e;
+        return Cache<std::vector<uint64_t>, KeySwitchHybrid>::get(
+            key, [&] { return std::make_shared<KeySwitchHybrid>(Q, P, numPartQ); });
     }
 };
 
@@ -1535,30 +1569,15 @@ public:
     };
     static std::shared_ptr<const Key> put(const std::string& id, DCRTPolyHip b, DCRTPolyHip a) {
         auto k = std::make_shared<const Key>(Key{std::move(b), std::move(a)});
-        std::lock_guard<std::mutex> lk(mu());
-        map()[id] = k;
+        NamedStore<Key>::put(id, k);
         return k;
     }
     static std::shared_ptr<const Key> get(const std::string& id) {
-        std::lock_guard<std::mutex> lk(mu());
-        auto it = map().find(id);
-        if (it == map().end()) throw math_error("KeyCache: no evaluation key '" + id + "'");
-        return it->second;
+        auto k = NamedStore<Key>::find(id);
+        if (!k) throw math_error("KeyCache: no evaluation key '" + id + "'");
+        return k;
     }
-    static void erase(const std::string& id) {
-        std::lock_guard<std::mutex> lk(mu());
-        map().erase(id);
-    }
-
-private:
-    static std::mutex& mu() {
-        static std::mutex m;
-        return m;
-    }
-    static std::map<std::string, std::shared_ptr<const Key>>& map() {
-        static std::map<std::string, std::shared_ptr<const Key>> m;
-        return m;
-    }
+    static void erase(const std::string& id) { NamedStore<Key>::erase(id); }
 };
 
 inline std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchHybrid::LinearTransform(const DCRTPolyHip& c0,
@@ -1566,9 +1585,7 @@ inline std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchHybrid::LinearTransform(cons
                                                                             const BsgsPlan& plan,
                                                                             const DCRTPolyHip& diag,
                                                                             uint64_t t) const {
-    if (c0.GetFormat() != Format::EVALUATION || c1.GetFormat() != Format::EVALUATION ||
-        diag.GetFormat() != Format::EVALUATION)
-        throw math_error("LinearTransform: EVALUATION form expected");
+    for (const DCRTPolyHip* v : {&c0, &c1, &diag}) check_form(*v, Format::EVALUATION, "LinearTransform");
     const size_t l = c0.GetParams()->Towers(), nb = plan.babyIndex.size(), ng = plan.giantIndex.size();
     if (l > sizeQ_ || c1.GetParams()->Moduli() != c0.GetParams()->Moduli() || c1.Batch() != c0.Batch())
         throw math_error("LinearTransform: c0 and c1 must be one ciphertext over Ql");
@@ -1580,43 +1597,36 @@ inline std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchHybrid::LinearTransform(cons
         throw math_error("LinearTransform: one presence byte per diagonal required");
     const uint64_t two_n = 2 * (uint64_t)c0.GetParams()->GetRingDimension();
     std::vector<std::shared_ptr<const KeyCache::Key>> hold;  // resident keys stay alive through the call
-    std::vector<const uint64_t*> kb[2], ka[2];
+    KeyPtrs k[2];  // baby, giant
     for (int g = 0; g < 2; g++) {
         const auto& idx = g ? plan.giantIndex : plan.babyIndex;
         const auto& ids = g ? plan.giantKey : plan.babyKey;
+        std::vector<RotationKey> keys(idx.size(), RotationKey{nullptr, nullptr});  // the identity steps stay NULL
         for (size_t i = 0; i < idx.size(); i++) {
-            if (idx[i] % two_n == 1) {
-                kb[g].push_back(nullptr);
-                ka[g].push_back(nullptr);
-                continue;
-            }
-            auto key = KeyCache::get(ids[i]);
-            if (key->b.Batch() != numPartQ_ || key->a.Batch() != numPartQ_ ||
-                key->b.GetParams()->Towers() != sizeQ_ + sizeP_ || key->a.GetParams()->Towers() != sizeQ_ + sizeP_)
-                throw math_error("LinearTransform: evaluation key must be numPartQ polynomials over Q|P");
-            kb[g].push_back(key->b.data());
-            ka[g].push_back(key->a.data());
-            hold.push_back(std::move(key));
+            if (idx[i] % two_n == 1) continue;
+            hold.push_back(KeyCache::get(ids[i]));
+            keys[i] = {&hold.back()->b, &hold.back()->a};
+            check_key("LinearTransform", keys[i].first, keys[i].second);
         }
+        k[g] = key_ptrs(keys);
     }
     ofhe_bsgs tr{};
     tr.nbaby = (uint32_t)nb;
     tr.ngiant = (uint32_t)ng;
     tr.baby_index = plan.babyIndex.data();
     tr.giant_index = plan.giantIndex.data();
-    tr.baby_key_b = kb[0].data();
-    tr.baby_key_a = ka[0].data();
-    tr.giant_key_b = kb[1].data();
-    tr.giant_key_a = ka[1].data();
+    tr.baby_key_b = k[0].b.data();
+    tr.baby_key_a = k[0].a.data();
+    tr.giant_key_b = k[1].b.data();
+    tr.giant_key_a = k[1].a.data();
     tr.diag = diag.data();
     tr.diag_stride = (uint64_t)(l + sizeP_) * c0.GetParams()->GetRingDimension();
     tr.present = plan.present.empty() ? nullptr : plan.present.data();
-    DCRTPolyHip o0(c0.GetParams(), Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{}),
-        o1(c0.GetParams(), Format::EVALUATION, c0.Batch(), DCRTPolyHip::Uninit{});
-    check(ofhe_hip_ks_bsgs_transform(h_, (uint32_t)l, &tr, c0.data(), c1.data(), o0.data(), o1.data(), t, c0.Batch(),
-                                     nullptr),
+    auto o = DCRTPolyHip::result_pair(c0.GetParams(), Format::EVALUATION, c0.Batch());
+    check(ofhe_hip_ks_bsgs_transform(h_.get(), (uint32_t)l, &tr, c0.data(), c1.data(), o.first.data(), o.second.data(),
+                                     t, c0.Batch(), nullptr),
           "LinearTransform");
-    return {std::move(o0), std::move(o1)};
+    return o;
 }
 
 // The tables of one level l of HPSPOVERQLEVELED as the reference's getters
@@ -1701,49 +1711,30 @@ public:
         : Q_(std::move(Q)), l_(T.l) {
         const size_t sizeQ = Q_->Towers(), L = (size_t)T.l + 1;
         if (L > sizeQ || R->Towers() < L) throw math_error("BfvLevel: l must be in [0, sizeQ - 1] and R hold l + 1 towers");
-        auto head = [&](const DCRTParams& P) {
-            return std::make_pair(std::vector<uint64_t>(P.Moduli().begin(), P.Moduli().begin() + L),
-                                  std::vector<uint64_t>(P.Roots().begin(), P.Roots().begin() + L));
-        };
-        auto ql = head(*Q_), rl = head(*R);
-        const uint32_t m = Q_->GetCyclotomicOrder();
-        const int dev = Q_->manager()->device();
-        Ql_ = std::make_shared<DCRTParams>(m, ql.first, ql.second, dev);
-        Rl_ = std::make_shared<DCRTParams>(m, rl.first, rl.second, dev);
-        ql.first.insert(ql.first.end(), rl.first.begin(), rl.first.end());
-        ql.second.insert(ql.second.end(), rl.second.begin(), rl.second.end());
-        QlRl_ = std::make_shared<DCRTParams>(m, ql.first, ql.second, dev);
+        Ql_ = Q_->Slice(0, L);
+        Rl_ = R->Slice(0, L);
+        QlRl_ = Ql_->Join(*Rl_);
         if (T.QlHatModq.size() != L) throw math_error("BfvLevel: QlHatModq must have l + 1 entries");
         ql_to_rl_.reset(new BaseConverter(*Ql_, *Rl_, T.QlHatInvModq, T.QlHatModr));
         rl_to_ql_.reset(new BaseConverter(*Rl_, *Ql_, T.RlHatInvModr, T.RlHatModq));
         neg_.reset(new BaseConverter(*Q_, *Rl_, T.negRlQHatInvModq, T.qInvModr));
-        if (L < sizeQ) {
-            DCRTParams dropped(m, std::vector<uint64_t>(Q_->Moduli().begin() + L, Q_->Moduli().end()),
-                               std::vector<uint64_t>(Q_->Roots().begin() + L, Q_->Roots().end()), dev);
-            drop_.reset(new ScaleAndRound(*Ql_, dropped, true, T.QlQHatInvModqDivqModq, T.QlQHatInvModqDivqFrac));
-        }
+        if (L < sizeQ)
+            drop_.reset(new ScaleAndRound(*Ql_, *Q_->Slice(L, sizeQ - L), true, T.QlQHatInvModqDivqModq,
+                                          T.QlQHatInvModqDivqFrac));
         sr_.reset(new ScaleAndRound(*Ql_, *Rl_, true, T.tQlSlHatInvModsDivsModq, T.tQlSlHatInvModsDivsFrac));
+        ofhe_bfv_level_t h = nullptr;
         check(ofhe_hip_bfv_level_create(Q_->manager()->ctx(), T.l, Q_->plan(), Ql_->plan(), Rl_->plan(), QlRl_->plan(),
                                         ql_to_rl_->handle(), rl_to_ql_->handle(), neg_->handle(),
-                                        drop_ ? drop_->handle() : nullptr, sr_->handle(), T.QlHatModq.data(), &h_),
+                                        drop_ ? drop_->handle() : nullptr, sr_->handle(), T.QlHatModq.data(), &h),
               "BfvLevel");
+        h_.reset(h);
     }
-    ~BfvLevel() {
-        if (h_) ofhe_hip_bfv_level_destroy(h_);
-    }
-    BfvLevel(const BfvLevel&) = delete;
-    BfvLevel& operator=(const BfvLevel&) = delete;
 
     // {cvMult[0], cvMult[1], cvMult[2]} over Q in COEFFICIENT form, as the reference leaves them
     std::vector<DCRTPolyHip> EvalMult(const DCRTPolyHip& c0, const DCRTPolyHip& c1, const DCRTPolyHip& d0,
                                       const DCRTPolyHip& d1) const {
-        for (const DCRTPolyHip* v : {&c0, &c1, &d0, &d1})
-            if (v->GetFormat() != Format::EVALUATION || v->GetParams()->Moduli() != Q_->Moduli() ||
-                v->Batch() != c0.Batch())
-                throw math_error("BfvLevel::EvalMult: EVALUATION-form ciphertexts over Q of one batch expected");
-        std::vector<DCRTPolyHip> out;
-        for (int k = 0; k < 3; k++) out.emplace_back(Q_, Format::COEFFICIENT, c0.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_bfv_eval_mult_leveled(h_, c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(),
+        auto out = bfv_mult_outputs("BfvLevel::EvalMult", Q_, c0, c1, d0, d1);
+        check(ofhe_hip_bfv_eval_mult_leveled(h_.get(), c0.data(), c1.data(), d0.data(), d1.data(), out[0].data(),
                                              out[1].data(), out[2].data(), c0.Batch(), nullptr),
               "BfvLevel::EvalMult");
         return out;
@@ -1762,22 +1753,21 @@ public:
             if (!v || v->GetFormat() != cv[0]->GetFormat() || v->GetParams()->Moduli() != Q_->Moduli() ||
                 v->Batch() != cv[0]->Batch())
                 throw math_error("BfvLevel::Relinearize: elements over Q in one format and of one batch expected");
-        DCRTPolyHip o0(Q_, Format::EVALUATION, cv[0]->Batch(), DCRTPolyHip::Uninit{}),
-            o1(Q_, Format::EVALUATION, cv[0]->Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_bfv_relinearize_leveled(h_, ks, (uint32_t)cv.size(), cv[0]->GetFormat() == Format::EVALUATION,
-                                               cv[0]->data(), cv[1]->data(), cv.size() == 3 ? cv[2]->data() : nullptr,
-                                               key_b.data(), key_a.data(), o0.data(), o1.data(), cv[0]->Batch(),
-                                               nullptr),
+        auto o = DCRTPolyHip::result_pair(Q_, Format::EVALUATION, cv[0]->Batch());
+        check(ofhe_hip_bfv_relinearize_leveled(h_.get(), ks, (uint32_t)cv.size(),
+                                               cv[0]->GetFormat() == Format::EVALUATION, cv[0]->data(), cv[1]->data(),
+                                               cv.size() == 3 ? cv[2]->data() : nullptr, key_b.data(), key_a.data(),
+                                               o.first.data(), o.second.data(), cv[0]->Batch(), nullptr),
               "BfvLevel::Relinearize");
-        return {std::move(o0), std::move(o1)};
+        return o;
     }
     // ScaleAndRound to Q_l and ExpandCRTBasisQlHat in one launch: x over Q_l R_l
     // (COEFFICIENT) -> Q
     DCRTPolyHip ScaleAndRoundExpand(const DCRTPolyHip& x) const {
         if (x.GetFormat() != Format::COEFFICIENT || x.GetParams()->Moduli() != QlRl_->Moduli())
             throw math_error("BfvLevel::ScaleAndRoundExpand: a COEFFICIENT-form polynomial over Ql|Rl expected");
-        DCRTPolyHip out(Q_, Format::COEFFICIENT, x.Batch(), DCRTPolyHip::Uninit{});
-        check(ofhe_hip_scale_round_expand_ql_hat(h_, x.data(), out.data(), x.Batch(), nullptr),
+        DCRTPolyHip out = DCRTPolyHip::result(Q_, Format::COEFFICIENT, x.Batch());
+        check(ofhe_hip_scale_round_expand_ql_hat(h_.get(), x.data(), out.data(), x.Batch(), nullptr),
               "BfvLevel::ScaleAndRoundExpand");
         return out;
     }
@@ -1791,20 +1781,19 @@ public:
     const BaseConverter& QToRlNeg() const { return *neg_; }
     const ScaleAndRound* Drop() const { return drop_.get(); }  // null at l = sizeQ - 1
     const ScaleAndRound& Scale() const { return *sr_; }
-    ofhe_bfv_level_t handle() const { return h_; }
+    ofhe_bfv_level_t handle() const { return h_.get(); }
 
 private:
     std::shared_ptr<DCRTParams> Q_, Ql_, Rl_, QlRl_;
     uint32_t l_;
     std::unique_ptr<BaseConverter> ql_to_rl_, rl_to_ql_, neg_;
     std::unique_ptr<ScaleAndRound> drop_, sr_;
-    ofhe_bfv_level_t h_ = nullptr;
+    Handle<ofhe_bfv_level_s, ofhe_hip_bfv_level_destroy> h_;
 };
 
 inline void DCRTPolyHip::ExpandCRTBasisQlHat(const BfvLevel& level) {
-    if (p_->Moduli() != level.ParamsQl()->Moduli() || p_->LogN() != level.ParamsQl()->LogN())
-        throw math_error("ExpandCRTBasisQlHat: the polynomial is not over the level's Q_l");
-    DCRTPolyHip r(level.ParamsQ(), f_, batch_, Uninit{});
+    check_over(*this, *level.ParamsQl(), "ExpandCRTBasisQlHat", ": the polynomial is not over the level's Q_l");
+    DCRTPolyHip r = result(level.ParamsQ(), f_, batch_);
     check(ofhe_hip_expand_ql_hat(level.handle(), data(), nullptr, r.data(), batch_, nullptr), "ExpandCRTBasisQlHat");
     *this = std::move(r);
 }
@@ -1818,15 +1807,11 @@ public:
     template <class F>
     static std::shared_ptr<BfvLevel> get(const std::shared_ptr<DCRTParams>& Q, const std::shared_ptr<DCRTParams>& R,
                                          uint64_t owner, uint32_t l, F&& tables) {
-        static std::mutex mu;
-        static std::map<std::vector<uint64_t>, std::shared_ptr<BfvLevel>> cache;
         std::vector<uint64_t> key{(uint64_t)Q->manager()->device(), Q->LogN(), owner, l, Q->Towers()};
         key.insert(key.end(), Q->Moduli().begin(), Q->Moduli().end());
         key.insert(key.end(), R->Moduli().begin(), R->Moduli().end());
-        std::lock_guard<std::mutex> lk(mu);
-        auto& e = cache[key];
-        if (!e) e = std::make_shared<BfvLevel>(Q, R, tables(l));
-        return e;
+        return Cache<std::vector<uint64_t>, BfvLevel>::get(key,
+                                                           [&] { return std::make_shared<BfvLevel>(Q, R, tables(l)); });
     }
 };
 

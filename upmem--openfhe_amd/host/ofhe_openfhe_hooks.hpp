@@ -288,9 +288,7 @@ bool MinusEq(Towers& a, const Towers& b, int device = 0) {
 
 // NTT plan over towers [t0, t0 + count) of a view (PlanCache: one per basis)
 inline std::shared_ptr<PlanHandle> plan_of(const TowerView& v, size_t t0, size_t count, int device) {
-    std::vector<uint64_t> q(v.q.begin() + t0, v.q.begin() + t0 + count);
-    std::vector<uint64_t> r(v.psi.begin() + t0, v.psi.begin() + t0 + count);
-    return PlanCache::get(device, v.log_n, q, r);
+    return PlanCache::get(device, v.log_n, towers_of(v.q, t0, count), towers_of(v.psi, t0, count));
 }
 
 // Base converter src -> dst with the pke layer's tables (rns-cryptoparameters.cpp
@@ -302,23 +300,18 @@ inline std::shared_ptr<ofhe_bconv_s> converter(int device, uint32_t log_n, const
     if (hinv.size() != src.size() || hmod.size() != src.size() * dst.size())
         throw math_error(std::string(what) + ": table sizes");
     HipManager* m = HipManager::getHip(device);
-    static std::mutex mu;
-    static std::map<std::vector<uint64_t>, std::shared_ptr<ofhe_bconv_s>> cache;
     std::vector<uint64_t> key{(uint64_t)device, log_n, src.size()};
     key.insert(key.end(), src.begin(), src.end());
     key.insert(key.end(), dst.begin(), dst.end());
     key.insert(key.end(), hinv.begin(), hinv.end());
     key.insert(key.end(), hmod.begin(), hmod.end());
-    std::lock_guard<std::mutex> lk(mu);
-    auto& e = cache[key];
-    if (!e) {
+    return Cache<std::vector<uint64_t>, ofhe_bconv_s>::get(key, [&]() -> std::shared_ptr<ofhe_bconv_s> {
         ofhe_bconv_t h = nullptr;
         check(ofhe_hip_bconv_create(m->ctx(), log_n, (uint32_t)src.size(), (uint32_t)dst.size(), src.data(), dst.data(),
                                     hinv.data(), hmod.data(), &h),
               what);
-        e = std::shared_ptr<ofhe_bconv_s>(h, [](ofhe_bconv_t p) { ofhe_hip_bconv_destroy(p); });
-    }
-    return e;
+        return Handle<ofhe_bconv_s, ofhe_hip_bconv_destroy>(h);
+    });
 }
 
 // DCRTPolyImpl::ApproxSwitchCRTBasis (dcrtpoly-impl.h:1034-1063): x's towers
@@ -363,8 +356,8 @@ bool ApproxModUp(Towers& towers, size_t sizeQ, const std::vector<uint64_t>& QHat
     TowerView v = view(towers);
     const size_t sizeP = v.q.size() - sizeQ;
     auto pq = plan_of(v, 0, sizeQ, device), pp = plan_of(v, sizeQ, sizeP, device);
-    std::vector<uint64_t> q(v.q.begin(), v.q.begin() + sizeQ), p(v.q.begin() + sizeQ, v.q.end());
-    auto bc = converter(device, v.log_n, q, p, QHatInvModq, QHatModp, "hooks::ApproxModUp");
+    auto bc = converter(device, v.log_n, towers_of(v.q, 0, sizeQ), towers_of(v.q, sizeQ, sizeP), QHatInvModq, QHatModp,
+                        "hooks::ApproxModUp");
     const size_t wx = sizeQ * (size_t)v.n, wo = v.q.size() * (size_t)v.n;
     Staging& sx = staging(device, wx, 0);
     Staging& so = staging(device, wo, 1);
@@ -399,8 +392,8 @@ bool ApproxModDown(const TowersQP& x, TowersQ& out, const std::vector<uint64_t>&
     if (PInvModq.size() != sizeQ) throw math_error("hooks::ApproxModDown: PInvModq size");
     const size_t sizeP = vx.q.size() - sizeQ;
     auto pq = plan_of(vx, 0, sizeQ, device), pp = plan_of(vx, sizeQ, sizeP, device);
-    std::vector<uint64_t> q(vx.q.begin(), vx.q.begin() + sizeQ), p(vx.q.begin() + sizeQ, vx.q.end());
-    auto bc = converter(device, vx.log_n, p, q, PHatInvModp, PHatModq, "hooks::ApproxModDown");
+    auto bc = converter(device, vx.log_n, towers_of(vx.q, sizeQ, sizeP), towers_of(vx.q, 0, sizeQ), PHatInvModp, PHatModq,
+                        "hooks::ApproxModDown");
     const size_t wx = vx.q.size() * (size_t)vx.n, wo = sizeQ * (size_t)vx.n;
     Staging& sx = staging(device, wx, 0);
     Staging& so = staging(device, wo, 1);
@@ -503,16 +496,6 @@ struct HookEvalKey {
     uint32_t num_part_q = 0;
     std::shared_ptr<const KeyCache::Key> key;
 };
-namespace detail {
-inline std::mutex& keys_mu() {
-    static std::mutex m;
-    return m;
-}
-inline std::map<std::string, std::shared_ptr<const HookEvalKey>>& keys() {
-    static std::map<std::string, std::shared_ptr<const HookEvalKey>> m;
-    return m;
-}
-}  // namespace detail
 
 // The EvalMultKeyGen / EvalAtIndexKeyGen side: uploads the key once, keyed by
 // its tag (Key::GetKeyTag).  bv[j] / av[j] are the tower vectors of
@@ -528,11 +511,10 @@ void PutEvalKey(const std::string& tag, const std::vector<const Towers*>& bv, co
     const size_t T = v0.q.size(), n = v0.n, dnum = bv.size();
     auto HK = std::make_shared<HookEvalKey>();
     const size_t sizeQ = T - sizeP;
-    HK->Q = std::make_shared<DCRTParams>(2 * (uint32_t)n, std::vector<uint64_t>(v0.q.begin(), v0.q.begin() + sizeQ),
-                                         std::vector<uint64_t>(v0.psi.begin(), v0.psi.begin() + sizeQ), device);
-    HK->P = std::make_shared<DCRTParams>(2 * (uint32_t)n, std::vector<uint64_t>(v0.q.begin() + sizeQ, v0.q.end()),
-                                         std::vector<uint64_t>(v0.psi.begin() + sizeQ, v0.psi.end()), device);
-    HK->QP = std::make_shared<DCRTParams>(2 * (uint32_t)n, v0.q, v0.psi, device);
+    const uint32_t m = 2 * (uint32_t)n;
+    HK->Q = std::make_shared<DCRTParams>(m, towers_of(v0.q, 0, sizeQ), towers_of(v0.psi, 0, sizeQ), device);
+    HK->P = std::make_shared<DCRTParams>(m, towers_of(v0.q, sizeQ, sizeP), towers_of(v0.psi, sizeQ, sizeP), device);
+    HK->QP = HK->Q->Join(*HK->P);
     HK->num_part_q = (uint32_t)dnum;
     std::vector<uint64_t> fb, fa;
     fb.reserve(dnum * T * n);
@@ -550,24 +532,20 @@ void PutEvalKey(const std::string& tag, const std::vector<const Towers*>& bv, co
             for (size_t t = 0; t < T; t++) f.insert(f.end(), vj.data[t], vj.data[t] + n);
         }
     }
-    DCRTPolyHip b(HK->QP, Format::EVALUATION, (uint32_t)dnum, DCRTPolyHip::Uninit{});
-    DCRTPolyHip a(HK->QP, Format::EVALUATION, (uint32_t)dnum, DCRTPolyHip::Uninit{});
-    b.SetValues(fb, Format::EVALUATION);
-    a.SetValues(fa, Format::EVALUATION);
-    HK->key = KeyCache::put("hooks:" + tag, std::move(b), std::move(a));
-    std::lock_guard<std::mutex> lk(detail::keys_mu());
-    detail::keys()[tag] = HK;
+    auto ba = DCRTPolyHip::result_pair(HK->QP, Format::EVALUATION, (uint32_t)dnum);
+    ba.first.SetValues(fb, Format::EVALUATION);
+    ba.second.SetValues(fa, Format::EVALUATION);
+    HK->key = KeyCache::put("hooks:" + tag, std::move(ba.first), std::move(ba.second));
+    NamedStore<HookEvalKey>::put(tag, HK);
 }
 inline void EraseEvalKey(const std::string& tag) {
     KeyCache::erase("hooks:" + tag);
-    std::lock_guard<std::mutex> lk(detail::keys_mu());
-    detail::keys().erase(tag);
+    NamedStore<HookEvalKey>::erase(tag);
 }
 inline std::shared_ptr<const HookEvalKey> GetEvalKey(const std::string& tag) {
-    std::lock_guard<std::mutex> lk(detail::keys_mu());
-    auto it = detail::keys().find(tag);
-    if (it == detail::keys().end()) throw math_error("hooks::KeySwitchCore: no resident evaluation key '" + tag + "'");
-    return it->second;
+    auto k = NamedStore<HookEvalKey>::find(tag);
+    if (!k) throw math_error("hooks::KeySwitchCore: no resident evaluation key '" + tag + "'");
+    return k;
 }
 
 // KeySwitchCore(a, evalKey) for the key PutEvalKey stored under `tag`: a's

@@ -264,6 +264,11 @@ def _arr(vals: Sequence[int]):
     return (ctypes.c_uint64 * len(vals))(*[int(v) for v in vals])
 
 
+def _ptrs(v):
+    """Host array of device pointers; None stays NULL, a 0 entry a NULL entry."""
+    return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
+
+
 def version() -> str:
     return lib().ofhe_hip_version().decode()
 
@@ -298,8 +303,28 @@ def _opt_ptr(o):
     return None if o is None else ctypes.cast(ctypes.byref(o), _vp)
 
 
-class Context:
+class _Handle:
+    """Owner of the C-ABI handle in ``_h``: close() destroys it once, through the symbol the class names."""
+
+    _destroy = ""
+    _h = None
+
+    def close(self) -> None:
+        if self._h is not None:
+            _check(getattr(lib(), self._destroy)(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """Per-device context (PimManager analogue)."""
+
+    _destroy = "ofhe_hip_finalize"
 
     def __init__(self, device: int = 0):
         h = _vp()
@@ -312,17 +337,6 @@ class Context:
         if self._h is None:
             raise MathError("context finalized")
         return self._h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_finalize(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def alloc(self, nbytes: int) -> int:
         p = _vp()
@@ -369,11 +383,13 @@ class Context:
         _check(lib().ofhe_hip_trim(self.handle, keep_bytes))
 
 
-class NTTPlan:
+class NTTPlan(_Handle):
     """Device-resident NTT tables for N = 2**log_n and one modulus per tower.
 
     Data buffers are [batch][towers][N] uint64 residues in device memory.
     """
+
+    _destroy = "ofhe_hip_plan_destroy"
 
     def __init__(self, ctx: Context, log_n: int, moduli: Sequence[int], roots: Sequence[int],
                  split: int = SPLIT_AUTO, generic_moduli: bool = False):
@@ -396,17 +412,6 @@ class NTTPlan:
         if self._h is None:
             raise MathError("plan destroyed")
         return self._h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_plan_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def tune(self, chunk_batch: int = 0, streams: int = 1) -> None:
         """Chunking / stream knob of ntt_mul_intt (speed only; results are identical)."""
@@ -537,8 +542,10 @@ class NTTPlan:
                                                  _vp(stream or None)))
 
 
-class BaseConverter:
+class BaseConverter(_Handle):
     """ApproxSwitchCRTBasis from basis Q (size_q towers) to basis P (size_p towers)."""
+
+    _destroy = "ofhe_hip_bconv_destroy"
 
     def __init__(self, ctx: Context, log_n: int, q: Sequence[int], p: Sequence[int],
                  qhat_inv_modq: Sequence[int], qhat_modp: Sequence[int], kernel: int = BCONV_KERNEL_AUTO,
@@ -553,17 +560,6 @@ class BaseConverter:
         _check(lib().ofhe_hip_bconv_create_ex(ctx.handle, self.log_n, self.size_q, self.size_p, _arr(q), _arr(p),
                                               _arr(qhat_inv_modq), _arr(qhat_modp), _opt_ptr(o), ctypes.byref(h)))
         self._h = h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_bconv_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def switch(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_approx_switch_crt_basis(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
@@ -595,11 +591,13 @@ def expand_crt_basis(plan_q: NTTPlan, plan_p: NTTPlan, q_to_p: BaseConverter, ev
                                            _vp(out), int(batch), _vp(stream or None)))
 
 
-class ScaleRound:
+class ScaleRound(_Handle):
     """DCRTPolyImpl::ScaleAndRound, DCRTPoly -> DCRTPoly (dcrtpoly-impl.h:1876-1955).  x is
     [batch][len(q) + len(p)][N], Q towers first, coefficient form; out_is_q = False (HPS) sums the Q
     towers into the P basis, True (HPSPOVERQ) the P towers into the Q basis.  int_table: size_o rows of
     size_i + 1 words (tOSHatInvModsDivsModo), frac: size_i doubles (tOSHatInvModsDivsFrac)."""
+
+    _destroy = "ofhe_hip_scale_round_destroy"
 
     def __init__(self, ctx: Context, log_n: int, q: Sequence[int], p: Sequence[int], out_is_q: bool,
                  int_table: Sequence[Sequence[int]], frac: Sequence[float]):
@@ -616,17 +614,6 @@ class ScaleRound:
                                                  ctypes.byref(h)))
         self._h = h
 
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_scale_round_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_scale_and_round(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
 
@@ -634,10 +621,12 @@ class ScaleRound:
 BFV_HPS, BFV_HPSPOVERQ = range(2)
 
 
-class BfvMult:
+class BfvMult(_Handle):
     """LeveledSHEBFVRNS::EvalMult (bfvrns-leveledshe.cpp:168-408) for two 2-element ciphertexts, technique
     HPS or HPSPOVERQ, composed from the caller's handles (kept alive by this object).  q_to_r_neg (the
     mNegRlQHatInvModq / qInvModr converter) is None for HPS."""
+
+    _destroy = "ofhe_hip_bfv_mult_destroy"
 
     def __init__(self, ctx: Context, technique: int, plan_q: NTTPlan, plan_r: NTTPlan, plan_qr: NTTPlan,
                  q_to_r: BaseConverter, r_to_q: BaseConverter, q_to_r_neg: Optional[BaseConverter],
@@ -650,17 +639,6 @@ class BfvMult:
                                               ctypes.byref(h)))
         self._h = h
 
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_bfv_mult_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def eval_mult(self, c0: int, c1: int, d0: int, d1: int, out0: int, out1: int, out2: int, batch: int = 1,
                   stream: int = 0) -> None:
         """Inputs [batch][Q][N] evaluation form; outputs [batch][Q][N] coefficient form."""
@@ -668,13 +646,15 @@ class BfvMult:
                                             _vp(out2), int(batch), _vp(stream or None)))
 
 
-class BfvLevel:
+class BfvLevel(_Handle):
     """One level l of HPSPOVERQLEVELED (l = the index of the last kept tower), composed from the
     caller's handles (kept alive by this object): plan_q over the full chain, plan_ql / plan_rl /
     plan_qlrl over Q_l, R_l and both, ql_to_rl / rl_to_ql with the true CRT tables, q_to_rl_neg (all
     size_q towers -> R_l with mNegRlQHatInvModq(l) / qInvModr), drop (ScaleRound Q -> Q_l, None at
     l = size_q - 1), scale_round (Q_l R_l -> Q_l) and ql_hat_modq ((Q / Q_l) mod q_i, i <= l).
     bfv_tables.LeveledTables holds every table."""
+
+    _destroy = "ofhe_hip_bfv_level_destroy"
 
     def __init__(self, ctx: Context, l: int, plan_q: NTTPlan, plan_ql: NTTPlan, plan_rl: NTTPlan, plan_qlrl: NTTPlan,
                  ql_to_rl: BaseConverter, rl_to_ql: BaseConverter, q_to_rl_neg: BaseConverter,
@@ -689,17 +669,6 @@ class BfvLevel:
                                                None if drop is None else drop._h, scale_round._h,
                                                _arr(ql_hat_modq), ctypes.byref(h)))
         self._h = h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_bfv_level_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def expand_ql_hat(self, x: int, out: int, addend: int = 0, batch: int = 1, stream: int = 0) -> None:
         """ExpandCRTBasisQlHat: x [batch][l + 1][N] -> out [batch][size_q][N], plus addend
@@ -745,7 +714,7 @@ class BehzTablesStruct(ctypes.Structure):
         "BModq")]
 
 
-class Behz:
+class Behz(_Handle):
     """The BEHZ variant of the BFV multiplication for ciphertext towers T.q, auxiliary towers T.b and
     T.msk (T: a ``bfv_tables.BehzTables``).  "Bsk" is the len(T.b) + 1 towers T.b + [T.msk].  Every
     array is [batch][towers][N] words of device memory.
@@ -759,6 +728,8 @@ class Behz:
       multiplication chooses (BEHZ_AUTO): [Q + Bsk] -> [Q].
     * ``eval_mult``  LeveledSHEBFVRNS::EvalMult, BEHZ (bfvrns-leveledshe.cpp:275-297, 383-403)."""
 
+    _destroy = "ofhe_hip_behz_destroy"
+
     def __init__(self, ctx: Context, log_n: int, T):
         self.ctx, self.log_n, self.tables = ctx, int(log_n), T
         self.size_q, self.size_b = len(T.q), len(T.b)
@@ -768,17 +739,6 @@ class Behz:
         _check(lib().ofhe_hip_behz_create(ctx.handle, self.log_n, self.size_q, _arr(T.q), self.size_b, _arr(T.bsk),
                                           int(T.t), ctypes.cast(ctypes.byref(ts), _vp), ctypes.byref(h)))
         self._h = h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_behz_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def q_to_bsk(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_behz_q_to_bsk(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
@@ -817,7 +777,7 @@ class BfvDecryptTablesStruct(ctypes.Structure):
                 ("negInvqModtgamma", _u64p), ("tInvModq", _u64p), ("negQModt", _u64p)]
 
 
-class BfvDecrypt:
+class BfvDecrypt(_Handle):
     """PKEBFVRNS::Decrypt (bfvrns-pke.cpp:205-248) and DCRTPolyImpl::TimesQovert for ciphertext towers T.q and
     plaintext modulus T.t (T: a ``bfv_tables.DecryptTables``), technique BFV_HPS / BFV_HPSPOVERQ or BFV_BEHZ.
     Tables the technique does not read, and members of T that are None, are not passed.
@@ -827,6 +787,8 @@ class BfvDecrypt:
       [Q][N] (evaluation form) -> out [batch][N].
     * ``times_q_over_t``   TimesQovert over [batch][Q][N]; out may be x.
     * ``branch``           the loop that runs: 0..7 for A..H, BFV_DECRYPT_BEHZ, BFV_DECRYPT_ONE_TOWER."""
+
+    _destroy = "ofhe_hip_bfv_decrypt_destroy"
 
     def __init__(self, ctx: Context, log_n: int, T, technique: int = BFV_HPS):
         self.ctx, self.log_n, self.tables, self.technique = ctx, int(log_n), T, int(technique)
@@ -853,17 +815,6 @@ class BfvDecrypt:
                                                  _arr(T.q), int(T.t), self.technique,
                                                  ctypes.cast(ctypes.byref(ts), _vp), ctypes.byref(h)))
         self._h = h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_bfv_decrypt_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def branch(self) -> int:
@@ -895,9 +846,11 @@ def approx_mod_down(plan_q: NTTPlan, plan_p: NTTPlan, p_to_q: BaseConverter, p_i
                                           _vp(x), _vp(out), int(batch), _vp(stream or None)))
 
 
-class KeySwitch:
+class KeySwitch(_Handle):
     """HYBRID key switching for ring 2**log_n, ciphertext moduli q (with roots
     rq), special moduli p (roots rp) and num_part_q digits."""
+
+    _destroy = "ofhe_hip_ks_destroy"
 
     def __init__(self, ctx: Context, log_n: int, q: Sequence[int], rq: Sequence[int], p: Sequence[int],
                  rp: Sequence[int], num_part_q: int, options: "KsOptions" = None):
@@ -911,17 +864,6 @@ class KeySwitch:
         _check(lib().ofhe_hip_ks_create_ex(ctx.handle, self.log_n, self.size_q, _arr(q), _arr(rq), self.size_p,
                                            _arr(p), _arr(rp), self.num_part_q, _opt_ptr(options), ctypes.byref(h)))
         self._h = h
-
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_ks_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def digits(self, size_ql: int):
         """(alpha, beta) at level size_ql."""
@@ -950,19 +892,16 @@ class KeySwitch:
     @staticmethod
     def _rot_args(auto_indices, key_b_ptrs, key_a_ptrs):
         """(nrot, index array, key pointer arrays) of the hoisted-rotation calls; None stays NULL."""
-        def ptrs(v):
-            return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
-
         for v in (key_b_ptrs, key_a_ptrs):
             if auto_indices is not None and v is not None and len(v) != len(auto_indices):
                 raise MathError("one evaluation key per automorphism index required")
         if auto_indices is None:
-            return 0, None, ptrs(key_b_ptrs), ptrs(key_a_ptrs)
+            return 0, None, _ptrs(key_b_ptrs), _ptrs(key_a_ptrs)
         for k in auto_indices:
             if not 0 <= int(k) < 1 << 32:
                 raise MathError("automorphism index must fit 32 bits")
         idx = (ctypes.c_uint32 * len(auto_indices))(*[int(k) for k in auto_indices])
-        return len(auto_indices), idx, ptrs(key_b_ptrs), ptrs(key_a_ptrs)
+        return len(auto_indices), idx, _ptrs(key_b_ptrs), _ptrs(key_a_ptrs)
 
     def fast_rotation_ext(self, size_ql: int, digits: int, c0: int, auto_indices: Sequence[int],
                           key_b_ptrs: Sequence[int], key_a_ptrs: Sequence[int], out0: int, out1: int,
@@ -1033,11 +972,6 @@ class KeySwitch:
                                                 _vp(c1 or None), _vp(out0 or None), _vp(out1 or None), int(t),
                                                 int(batch), _vp(stream or None)))
 
-    @staticmethod
-    def _ptrs(v):
-        """Host array of device pointers; None stays NULL, a 0 entry a NULL entry."""
-        return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
-
     def eval_mult(self, size_ql: int, c0: int, c1: int, d0: int, d1: int, key_b: int, key_a: int, out0: int,
                   out1: int, scheme: int = SHE_CKKS, t: int = 0, levels: int = 0, batch: int = 1,
                   stream: int = 0) -> None:
@@ -1063,8 +997,8 @@ class KeySwitch:
         for v in (key_b_ptrs, key_a_ptrs):
             if v is not None and elements is not None and n >= 2 and len(v) != n - 2:
                 raise MathError("one evaluation key per element past the second required")
-        _check(lib().ofhe_hip_ks_relinearize(self._h, int(size_ql), n, self._ptrs(elements), self._ptrs(key_b_ptrs),
-                                             self._ptrs(key_a_ptrs), _vp(out0 or None), _vp(out1 or None), int(t),
+        _check(lib().ofhe_hip_ks_relinearize(self._h, int(size_ql), n, _ptrs(elements), _ptrs(key_b_ptrs),
+                                             _ptrs(key_a_ptrs), _vp(out0 or None), _vp(out1 or None), int(t),
                                              int(batch), _vp(stream or None)))
 
     def rescale(self, size_ql: int, x_ptrs: Sequence[int], out_ptrs: Sequence[int], scheme: int = SHE_CKKS,
@@ -1075,7 +1009,7 @@ class KeySwitch:
             raise MathError("one output per element required")
         n = 0 if x_ptrs is None else len(x_ptrs)
         _check(lib().ofhe_hip_ks_rescale(self._h, int(size_ql), int(scheme), int(t), int(levels), n,
-                                         self._ptrs(x_ptrs), self._ptrs(out_ptrs), int(batch), _vp(stream or None)))
+                                         _ptrs(x_ptrs), _ptrs(out_ptrs), int(batch), _vp(stream or None)))
 
 
 def comm_unique_id() -> bytes:
@@ -1085,9 +1019,11 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class Comm:
+class Comm(_Handle):
     """RCCL communicator of this process's device (ofhe_hip_comm_init).
     Collective: every rank constructs it with the same id."""
+
+    _destroy = "ofhe_hip_comm_destroy"
 
     def __init__(self, ctx: Context, nranks: int, rank: int, uid: bytes):
         if len(uid) != COMM_ID_BYTES:
@@ -1104,13 +1040,3 @@ class Comm:
         _check(lib().ofhe_hip_bcast_evalkey(self._h, _vp(key_ptr or None), int(words), int(root),
                                             _vp(stream or None)))
 
-    def close(self) -> None:
-        if self._h is not None:
-            _check(lib().ofhe_hip_comm_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
