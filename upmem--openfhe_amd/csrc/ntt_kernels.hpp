@@ -423,7 +423,7 @@ __device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[16], const u64* tw3, u32
 // to all sets before the next fetch, as cols_fwd's columns.  Per set, the
 // operations and their order are those of the one-set helpers above.
 // ---------------------------------------------------------------------------
-template <int S, int Q, class M_>
+template <int S, int Q, class M_, int CS = S & 1>
 __device__ __forceinline__ void fwd_stage16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
     constexpr int half = 8 >> S;
     const u64* base = tw + 2 * ((u64)M0 << S);
@@ -433,13 +433,20 @@ __device__ __forceinline__ void fwd_stage16(u64 (&v)[Q][16], const u64* tw, u32 
 #pragma unroll
         for (int k = j * 2 * half; k < j * 2 * half + half; k++)
 #pragma unroll
-            for (int c = 0; c < Q; c++) ct_bfly<S & 1>(v[c][k], v[c][k + half], w, M);
+            for (int c = 0; c < Q; c++) ct_bfly<CS>(v[c][k], v[c][k + half], w, M);
     }
 }
 template <int Q, class M_>
 __device__ __forceinline__ void fwd_round16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
     fwd_stage16<0>(v, tw, M0, M);
     fwd_stage16<1>(v, tw, M0, M);
+    fwd_stage16<2>(v, tw, M0, M);
+    fwd_stage16<3>(v, tw, M0, M);
+}
+template <int Q, class M_>
+__device__ __forceinline__ void fwd_round16_canon(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    fwd_stage16<0>(v, tw, M0, M);
+    fwd_stage16<1, Q, M_, 0>(v, tw, M0, M);
     fwd_stage16<2>(v, tw, M0, M);
     fwd_stage16<3>(v, tw, M0, M);
 }
@@ -997,12 +1004,71 @@ static_assert(TCOLS_W == 16 || TCOLS_W == 32, "column tile width");
 // same 256-row sub-transforms on 512 columns (the twiddle index of stage m is
 // m + row / (256 / m) whatever the row length).
 constexpr u32 TCOLS_LDS_WORDS = 16 * 16 * TCOLS_W + 16 * 16;
+#ifndef OFHE_TCOLS_CPT
+#define OFHE_TCOLS_CPT 2  // columns per thread of the forward pass at N = 2^16 without a lift: 1 or 2
+#endif
+constexpr int TCOLS_CPT = OFHE_TCOLS_CPT;
+static_assert(TCOLS_CPT == 1 || TCOLS_CPT == 2, "columns per thread");
+static_assert(TCOLS_CPT == 1 || TCOLS_W == 16, "two columns per thread: 16 column pairs per tile row");
+// Two columns per thread (CPT = 2; forward, N = 2^16, no lift): the tile is 32
+// columns x 256 rows and thread (h, r) holds v[c][k] of columns 2r + c, so
+// every global access moves 16 bytes per lane (256-byte row segments) and
+// every twiddle -- a function of the row alone -- is fetched once for both
+// columns.  The two column sets go through the CPT = 1 tile (same patterns,
+// same padding) one after the other, so the kernel keeps 34 816 bytes of LDS
+// and four workgroups per CU.  Per column the operations and their order are
+// those of the CPT = 1 body.  The inverse pass stays at one column per thread
+// (rejected variants).
+template <bool SPQ>
+__device__ __forceinline__ void tcols_pairs_fwd(const PlanArgs& P, const u64* src, u64* dst, u32 batch, u32 wid,
+                                                u64* lds, u32 tid) {
+    constexpr u32 N = 1u << 16, S = 256, W = 16, TILES = S / (2 * W), RP = 16 * W + 16;
+    const u32 cb = wid % TILES;
+    const u32 pb = wid / TILES;
+    const u32 t = pb / batch, b = pb % batch;
+    const u32 h = tid / W, r = tid % W;
+    const u64 inner = (u64)t * N + cb * 2 * W + 2 * r;  // even: 16-byte accesses (launch_colpass checks the rest)
+    const u64* x = src + (u64)b * P.sstride + inner;
+    u64* y = dst + (u64)b * P.dstride + inner;
+    const TowerConst tc = P.tc[t];
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
+    const u64* tw = P.tw + (u64)t * N * 2;
+    u64 v[2][16];
+    // round 1: rows h + 16k, stages m = 1..8
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const u64x2 e = ld2_s(x + (u64)(h + 16 * k) * S);
+        v[0][k] = e.x;
+        v[1][k] = e.y;
+    }
+    fwd_round16_canon(v, tw, 1, M);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        if (c) __syncthreads();  // every thread has read set 0
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[tid + RP * k] = v[c][k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[c][k] = lds[h * RP + r + W * k];
+    }
+    // round 2: rows 16h + k, stages m = 16..128
+    fwd_round16(v, tw, 16 + h, M);
+#pragma unroll
+    for (int k = 0; k < 16; k++) st2_s(y + (u64)(16 * h + k) * S, u64x2{v[0][k], v[1][k]});
+}
 // The body of k_tcols for work item wid (column tile cb = wid % (S / W) of
-// polynomial tower pb = wid / (S / W)) on the caller's LDS (TCOLS_LDS_WORDS).
-template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16>
+// polynomial tower pb = wid / (S / W), W CPT columns per tile) on the caller's
+// LDS (TCOLS_LDS_WORDS).
+template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16, int CPT = 1>
 __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u64* dst, u32 batch, u32 wid,
                                            const SwSrc& SWA, u64* lds, u32 tid) {
     static_assert(LOGN == 16 || LOGN == 17, "k_tcols: N = 2^16 or 2^17");
+    static_assert(CPT == 1 || (CPT == 2 && !INV && LOGN == 16 && !SWS && TCOLS_W == 16),
+                  "two columns per thread: forward, N = 2^16, no lift");
+    if constexpr (CPT == 2) {
+        tcols_pairs_fwd<SPQ>(P, src, dst, batch, wid, lds, tid);
+        return;
+    }
     constexpr u32 N = 1u << LOGN, S = N / 256, W = TCOLS_W;
     // Exchange patterns p = tid + 16W k (round 1) and p = 16W h + W k + r
     // (round 2).  The inverse writes the second and reads the first: unpadded,
@@ -1077,12 +1143,12 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
     }
 }
 
-template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16>
+template <bool INV, bool SPQ, bool SWS = false, int LOGN = 16, int CPT = 1>
 __global__ __launch_bounds__(16 * TCOLS_W, OFHE_KB_WAVES) void k_tcols(PlanArgs P, const u64* src, u64* dst, u32 batch,
                                                                        u32 nwg, SwSrc SWA) {
     OFHE_VGPR_FLOOR();
     __shared__ u64 lds[TCOLS_LDS_WORDS];
-    tcols_body<INV, SPQ, SWS, LOGN>(P, src, dst, batch, xcd_remap(blockIdx.x, nwg), SWA, lds, threadIdx.x);
+    tcols_body<INV, SPQ, SWS, LOGN, CPT>(P, src, dst, batch, xcd_remap(blockIdx.x, nwg), SWA, lds, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------

@@ -562,12 +562,19 @@ static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, con
                     hipLaunchKernelGGL((k_tcols9<INV, SP>), dim3(nwg), dim3(512), 0, s, a, src, dst, batch, nwg);
                 }
             } else if (split != SPLIT_COLS) {
-                with_int<16, 17>(split == SPLIT_T8B9 ? 17 : 16, [&](auto ln) {
+                // the forward pass at N = 2^16 without a lift runs two columns per
+                // thread (16-byte accesses) when every row segment of src and dst
+                // is 16-byte aligned; any other call runs one column per thread
+                // and gives the same words
+                const bool pairs = TCOLS_CPT == 2 && !inv && split == SPLIT_T8 && !lift &&
+                                   !(((uintptr_t)src | (uintptr_t)dst) & 15) && !((a.sstride | a.dstride) & 1);
+                with_int<16, 17>(split == SPLIT_T8B9 ? 17 : 16, [&](auto ln) { with_bool(pairs, [&](auto pr) {
                     constexpr int LOGN = decltype(ln)::value;
-                    const u32 nwg = polys * ((1u << (LOGN - 8)) / TCOLS_W);  // 256 or 512 columns
-                    hipLaunchKernelGGL((k_tcols<INV, SP, SWS, LOGN>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a, src,
-                                       dst, batch, nwg, S);
-                });
+                    constexpr int CPT = (decltype(pr)::value && !INV && LOGN == 16 && !SWS) ? TCOLS_CPT : 1;
+                    const u32 nwg = polys * ((1u << (LOGN - 8)) / (TCOLS_W * CPT));  // 256 or 512 columns
+                    hipLaunchKernelGGL((k_tcols<INV, SP, SWS, LOGN, CPT>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
+                                       src, dst, batch, nwg, S);
+                }); });
             } else {
                 with_int<1, 2, 3, 4, 5>((int)a.log_n - 12, [&](auto ka) {
                     // two columns per thread (16-byte accesses) while registers allow
