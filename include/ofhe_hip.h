@@ -528,6 +528,58 @@ int ofhe_hip_bv_core(ofhe_plan_t plan, uint32_t towers, const uint64_t* digits, 
                      const uint64_t* key_a, uint32_t key_towers, uint64_t* out0, uint64_t* out1, uint32_t batch,
                      void* stream);
 
+/* ---- BV key switching with a digit size (digitSize = r, base-2^r digits;
+ *      DCRTPolyImpl::CRTDecompose(r), dcrtpoly-impl.h:266-320) ----
+ * Tower i of c in coefficient form is cut into w_i = ceil(bitlen(q_i) / r)
+ * windows win_{i,j}[x] = (coef_i[x] >> (j r)) & (2^r - 1)
+ * (PolyImpl::BaseDecompose, poly-impl.h:516-542).  Digit arrWindows[i] + j,
+ * arrWindows[i] = w_0 + ... + w_{i-1}, holds win_{i,j} in tower i and
+ * SwitchModulus(win_{i,j}, q_i -> q_k) in every tower k != i, in evaluation
+ * form.  digit_size = 0 is the setting of the two calls above (one digit per
+ * tower) and gives their words; digit_size > 30 has no defined reference
+ * behaviour (1 << digitSize in an int) and is refused with OFHE_ERR_ARG.
+ * Every data buffer is 16-byte aligned.  The argument rules that need no plan
+ * (NULL pointers, batch == 0, alignment, digit_size > 30, count == NULL,
+ * n_digits == 0, key_towers < towers, digits given as an output) are checked
+ * before the plan and return OFHE_ERR_ARG; a NULL plan after those returns
+ * OFHE_ERR_STATE.
+ *
+ * The reference's nWindows over the plan's first `towers` moduli. */
+int ofhe_hip_bv_digit_count(ofhe_plan_t plan, uint32_t towers, uint32_t digit_size, uint32_t* count);
+/* KeySwitchBV::EvalKeySwitchPrecomputeCore: c [batch][towers][N] in evaluation
+ * form -> digits [batch][n_digits][towers][N] in evaluation form, in the
+ * reference's digit order, n_digits = ofhe_hip_bv_digit_count. */
+int ofhe_hip_bv_precompute_digits(ofhe_plan_t plan, uint32_t towers, uint32_t digit_size, const uint64_t* c,
+                                  uint64_t* digits, uint32_t batch, void* stream);
+/* KeySwitchBV::EvalFastKeySwitchCore (keyswitch-bv.cpp:314-338) over n_digits
+ * digits: out0 = sum_d key_b[d] * digit_d, out1 = sum_d key_a[d] * digit_d.
+ * The keys are [key_digits][key_towers][N]; the first `towers` towers of the
+ * first n_digits polynomials are used (a lower level's digits are a prefix of
+ * the key's numbering).  Any n_digits up to the digit count of these towers at
+ * digit_size = 1: the sum is exact in 128 bits and folded every 256 terms. */
+int ofhe_hip_bv_core_digits(ofhe_plan_t plan, uint32_t towers, uint32_t n_digits, const uint64_t* digits,
+                            const uint64_t* key_b, const uint64_t* key_a, uint32_t key_towers,
+                            uint64_t* out0, uint64_t* out1, uint32_t batch, void* stream);
+/* KeySwitchBV::KeySwitchInPlace (keyswitch-bv.cpp:283-300) in one call:
+ * out0 = add0 + ct0, out1 = add1 + ct1 with (ct0, ct1) the two sums above over
+ * the digits of c.  add0 / add1: [batch][towers][N], canonical, NULL for zero,
+ * and each may be its own output (a two-element ciphertext passes add1 = NULL,
+ * a three-element one its first two elements); an output may also be c itself.
+ * The whole digit array is never held: the decomposition and the inner product
+ * run over chunk_digits digits at a time, each chunk adding into the outputs,
+ * and the result does not depend on chunk_digits.  chunk_digits = 0 takes the
+ * most digits whose [batch][chunk][towers][N] words fit in 1 GiB of scratch
+ * (at least one). */
+int ofhe_hip_bv_key_switch(ofhe_plan_t plan, uint32_t towers, uint32_t digit_size, const uint64_t* c,
+                           const uint64_t* key_b, const uint64_t* key_a, uint32_t key_towers,
+                           const uint64_t* add0, const uint64_t* add1, uint64_t* out0, uint64_t* out1,
+                           uint32_t chunk_digits, uint32_t batch, void* stream);
+/* Tuning knob of the inner product above, process-wide: the batch entries whose
+ * accumulators one thread holds while it loads each key word pair once
+ * (key-stationary).  0: the library's choice per batch size; 1: the plain loop;
+ * 2 or 4.  The results are the same words under every setting. */
+int ofhe_hip_bv_tune(uint32_t key_stationary);
+
 /* ---- BFV multiplication, HPS family: what LeveledSHEBFVRNS::EvalMult
  *      (pke/lib/scheme/bfvrns/bfvrns-leveledshe.cpp:168-408) runs between the
  *      tensor product and key switching.  All results are bit-exact with the

@@ -11,11 +11,14 @@
 //   LeveledSHEBase::EvalMult / EvalSquare / Relinearize (with evaluation keys)
 //                                                 base-leveledshe.cpp:199-372
 //   ModReduceInternalInPlace   ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77
+//   KeySwitchBV (digitSize 0 .. 30)  keyswitch-bv.cpp:283-338, DCRTPolyImpl::CRTDecompose dcrtpoly-impl.h:266-320
 // CRT tables follow CryptoParametersRNS::PrecomputeCRTTables
 // (rns-cryptoparameters.cpp:72-345).  The reference builds them with
 // BigInteger quotients (Q/q_i) and reductions; every table entry is a residue
 // of a product of the moduli, so it is computed here as that product reduced
 // modulo the target prime -- the same integer.
+#include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <new>
 
@@ -1329,6 +1332,253 @@ int ofhe_hip_bv_core(ofhe_plan_t p, uint32_t towers, const uint64_t* digits, con
     RCCHK(coeff_grid((u64)bpr * batch * towers * 256, &g, "batch too large for one launch"));
     hipLaunchKernelGGL(k_bv_inner, g, dim3(256), 0, pick(stream), A, bpr);
     return post_launch();
+}
+
+// ---------------------------------------------------------------------------
+// BV key switching with a digit size r (CRTDecompose(r), dcrtpoly-impl.h:
+// 266-320): tower i of c in coefficient form is cut into w_i = ceil(bitlen(q_i)
+// / r) windows of r bits (k_bv_windows), digit arrWindows[i] + j is window j of
+// tower i lifted into every tower (SwitchModulus q_i -> q_k: a window can
+// exceed q_i / 2 or q_k) and transformed -- the lift + forward NTT of
+// ofhe_hip_bv_precompute, fed by window rows instead of tower rows.  r = 0, and
+// any tower with a single window (that window is the tower), is lifted from
+// the coefficient rows directly, so r = 0 gives ofhe_hip_bv_precompute's words.
+// ---------------------------------------------------------------------------
+static u32 bv_windows(u64 q, u32 r) { return r ? (msb64(q) + r - 1) / r : 1; }  // GetLengthForBase(2) = bit length
+static u32 bv_digits(const u64* q, u32 towers, u32 r) {
+    u32 n = 0;
+    for (u32 i = 0; i < towers; i++) n += bv_windows(q[i], r);
+    return n;
+}
+
+// Scratch bound of ofhe_hip_bv_key_switch with chunk_digits = 0: the chunk is the
+// largest number of digits whose [batch][chunk][towers][N] words fit in it (at
+// least one digit, at most all).  1 GiB: every chunk re-reads and re-writes the
+// two outputs, and at N = 2^16, 16 towers, batch 4 chunks of 8 digits (256 MiB)
+// measured 7 % behind the whole array, chunks of 32 within 2 %.
+constexpr u64 BV_CHUNK_SCRATCH_BYTES = 1ull << 30;
+
+// Key-stationary batch entries per thread of the inner product (ofhe_hip_bv_tune):
+// 0 picks by batch size (bv_inner_nb), 1 is the plain loop.
+static std::atomic<u32> g_bv_nb{0};
+// The measured choice (tools/bv_digits_ab.py, DESIGN.md "BV key switching with a
+// digit size"): the key-stationary kernel wins once the batch gives it several
+// entries per thread and the launch still has BV_KS_MIN_THREADS threads; below
+// that the grid is too small to keep the memory system busy and the plain loop
+// (one thread per output word) is as fast or faster.
+constexpr u64 BV_KS_MIN_THREADS = 1ull << 19;
+static u32 bv_inner_nb(u32 batch, u32 towers, u32 log_n) {
+    const u32 forced = g_bv_nb.load(std::memory_order_relaxed);
+    if (forced) return forced;
+    for (u32 nb : {4u, 2u})
+        if (batch >= nb && ((u64)((batch + nb - 1) / nb) * towers << log_n) >= BV_KS_MIN_THREADS) return nb;
+    return 1;
+}
+
+int ofhe_hip_bv_tune(uint32_t key_stationary) {
+    if (key_stationary != 0 && key_stationary != 1 && key_stationary != 2 && key_stationary != 4)
+        return fail(OFHE_ERR_ARG, "key_stationary must be 0 (auto), 1 (plain), 2 or 4");
+    g_bv_nb.store(key_stationary, std::memory_order_relaxed);
+    return OFHE_OK;
+}
+
+// the lift of `nb` rows (last + b * lstride, modulus ql) into the T towers of y + b * ystride, transformed
+static int bv_lift(ofhe_plan_t p, u32 T, const u64* dsw, const u64* last, u64 lstride, u64 ql, u64* y, u64 ystride,
+                   u32 nb, hipStream_t s) {
+    const u32 log_n = p->log_n;
+    if (log_n > 12 && p->split != SPLIT_T9) {
+        RCCHK(plan_cols_switch(p, 0, T, last, lstride, ql, 1, dsw, y, ystride, nb, s));
+        return plan_ntt_fwd_block(p, 0, T, y, ystride, nb, s);
+    }
+    const u64 N = 1ull << log_n;
+    const u32 bpr = (u32)((N / 2 + 255) / 256);
+    dim3 g;
+    RCCHK(coeff_grid((u64)bpr * nb * T * 256, &g, "batch too large for one launch"));
+    SwArgs A{};
+    A.last = last;
+    A.lstride = lstride;
+    A.y = y;
+    A.ystride = ystride;
+    A.tab = dsw;
+    A.ql = ql;
+    A.pre = 1;
+    A.log_n = log_n;
+    A.towers = T;
+    hipLaunchKernelGGL(k_switch_scale<SW_SCALE>, g, dim3(256), 0, s, A, bpr);
+    RCCHK(post_launch());
+    return plan_ntt_range(p, false, 0, T, y, y, ystride, ystride, nb, s);
+}
+
+// Digits [d0, d1) of CRTDecompose(r) of sc (c in coefficient form, [batch][T][N])
+// into dig [batch][d1 - d0][T][N].  The windows of one source tower are lifted
+// together: one launch pair with the windows as the batch (batch = 1), else
+// one per batch entry or one per window, whichever is fewer.
+static int bv_decompose_range(ofhe_plan_t p, u32 T, u32 r, const u64* sc, u32 d0, u32 d1, u64* dig, u32 batch,
+                              hipStream_t s) {
+    const u32 log_n = p->log_n, nc = d1 - d0;
+    const u64 N = 1ull << log_n, TN = (u64)T * N;
+    const u64* dsw = nullptr;
+    RCCHK(plan_table(p, rs_build(p->q.data(), T, SW_SCALE, true, nullptr, nullptr, 0).sw, &dsw));
+    u32 maxw = 0;  // the most windows any tower contributes to the range
+    for (u32 i = 0, a = 0; i < T; a += bv_windows(p->q[i], r), i++) {
+        const u32 w = bv_windows(p->q[i], r), lo = std::max(a, d0), hi = std::min(a + w, d1);
+        if (w > 1 && lo < hi) maxw = std::max(maxw, hi - lo);
+    }
+    Scratch sw;  // [batch][nw][N] window rows of one tower at a time
+    if (maxw) RCCHK(sw.alloc((size_t)batch * maxw * N * 8, s, p->ctx));
+    const u32 bpr = (u32)((N / 2 + 255) / 256);
+    for (u32 i = 0, a = 0; i < T; a += bv_windows(p->q[i], r), i++) {
+        const u32 w = bv_windows(p->q[i], r), lo = std::max(a, d0), hi = std::min(a + w, d1);
+        if (lo >= hi) continue;
+        const u32 nw = hi - lo, e0 = lo - d0;
+        const u64 qi = p->q[i];
+        if (w == 1) {
+            RCCHK(bv_lift(p, T, dsw, sc + (u64)i * N, TN, qi, dig + (u64)e0 * TN, (u64)nc * TN, batch, s));
+            continue;
+        }
+        BvWinArgs W{sc + (u64)i * N, TN, sw.w(), r, lo - a, nw, log_n};
+        dim3 g;
+        RCCHK(coeff_grid((u64)bpr * batch * 256, &g, "batch too large for one launch"));
+        hipLaunchKernelGGL(k_bv_windows, g, dim3(256), 0, s, W, bpr);
+        RCCHK(post_launch());
+        if (batch <= nw) {
+            for (u32 b = 0; b < batch; b++)
+                RCCHK(bv_lift(p, T, dsw, sw.w() + (u64)b * nw * N, N, qi, dig + ((u64)b * nc + e0) * TN, TN, nw, s));
+        } else {
+            for (u32 j = 0; j < nw; j++)
+                RCCHK(bv_lift(p, T, dsw, sw.w() + (u64)j * N, (u64)nw * N, qi, dig + (u64)(e0 + j) * TN, (u64)nc * TN,
+                              batch, s));
+        }
+    }
+    return OFHE_OK;
+}
+
+// out = acc + sum_{d < nd} key[k0 + d] . digit_d (k_bv_inner_digits); acc NULL: zero
+static int bv_inner_run(ofhe_plan_t p, u32 T, u32 nd, const u64* digits, const u64* kb, const u64* ka, u32 key_towers,
+                        const u64* acc0, const u64* acc1, u64* out0, u64* out1, u32 batch, hipStream_t s) {
+    std::vector<u64> mu(3 * (size_t)T);
+    for (u32 t = 0; t < T; t++) {
+        mu[3 * t] = p->q[t];
+        barrett128(p->q[t], &mu[3 * t + 1]);
+    }
+    const u64* dmu = nullptr;
+    RCCHK(plan_table(p, mu, &dmu));
+    BvDigitArgs D{BvArgs{digits, kb, ka, out0, out1, dmu, nd, T, key_towers, p->log_n}, acc0, acc1, batch};
+    const u64 N = 1ull << p->log_n;
+    const u32 bpr = (u32)((N + 255) / 256);
+    const u32 nb = bv_inner_nb(batch, T, p->log_n);
+    dim3 g;
+    RCCHK(coeff_grid((u64)bpr * ((batch + nb - 1) / nb) * T * 256, &g, "batch too large for one launch"));
+    with_int<1, 2, 4>((int)nb, [&](auto n) {
+        hipLaunchKernelGGL(k_bv_inner_digits<decltype(n)::value>, g, dim3(256), 0, s, D, bpr);
+    });
+    return post_launch();
+}
+
+static bool bv_aligned(std::initializer_list<const void*> ps) {
+    for (const void* x : ps)
+        if ((uintptr_t)x & 15) return false;
+    return true;
+}
+static int bv_plan_check(ofhe_plan_t p, u32 towers) {
+    if (!p || !p->ctx) return fail(OFHE_ERR_STATE, "plan is NULL or destroyed");
+    if (towers < 1 || towers > p->towers) return fail(OFHE_ERR_ARG, "towers must be in [1, plan towers]");
+    return OFHE_OK;
+}
+static const char* const BV_DIGIT_SIZE_MSG = "digit_size must be at most 30 (the reference forms 1 << digitSize in an int)";
+
+int ofhe_hip_bv_digit_count(ofhe_plan_t p, uint32_t towers, uint32_t digit_size, uint32_t* count) {
+    if (digit_size > 30) return fail(OFHE_ERR_ARG, BV_DIGIT_SIZE_MSG);
+    if (!count) return fail(OFHE_ERR_ARG, "count is NULL");
+    RCCHK(bv_plan_check(p, towers));
+    *count = bv_digits(p->q.data(), towers, digit_size);
+    return OFHE_OK;
+}
+
+int ofhe_hip_bv_precompute_digits(ofhe_plan_t p, uint32_t towers, uint32_t digit_size, const uint64_t* c,
+                                  uint64_t* digits, uint32_t batch, void* stream) {
+    if (!c || !digits || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
+    if (!bv_aligned({c, digits})) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    if (digit_size > 30) return fail(OFHE_ERR_ARG, BV_DIGIT_SIZE_MSG);
+    RCCHK(bv_plan_check(p, towers));
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t s = pick(stream);
+    const u64 TN = (u64)towers << p->log_n;
+    Scratch sc;  // c in coefficient form
+    RCCHK(sc.alloc((size_t)batch * TN * 8, s, p->ctx));
+    RCCHK(plan_ntt_range(p, true, 0, towers, c, sc.w(), TN, TN, batch, s));
+    return bv_decompose_range(p, towers, digit_size, sc.w(), 0, bv_digits(p->q.data(), towers, digit_size), digits,
+                              batch, s);
+}
+
+int ofhe_hip_bv_core_digits(ofhe_plan_t p, uint32_t towers, uint32_t n_digits, const uint64_t* digits,
+                            const uint64_t* key_b, const uint64_t* key_a, uint32_t key_towers, uint64_t* out0,
+                            uint64_t* out1, uint32_t batch, void* stream) {
+    if (!digits || !key_b || !key_a || !out0 || !out1 || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
+    if (!bv_aligned({digits, key_b, key_a, out0, out1})) return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    if (n_digits == 0) return fail(OFHE_ERR_ARG, "n_digits must be >= 1");
+    if (key_towers < towers) return fail(OFHE_ERR_ARG, "key_towers smaller than towers");
+    if (digits == out0 || digits == out1 || out0 == out1)
+        return fail(OFHE_ERR_ARG, "digits, out0 and out1 must be distinct buffers");
+    RCCHK(bv_plan_check(p, towers));
+    // the finest decomposition (digit_size = 1) bounds every digit count
+    if (n_digits > bv_digits(p->q.data(), towers, 1))
+        return fail(OFHE_ERR_ARG, "n_digits exceeds the digit count of these towers at digit_size = 1");
+    const u64 w = (u64)batch * towers << p->log_n;
+    RCCHK(outputs_apart(out0, out1, w));
+    if (words_overlap(digits, w * n_digits, out0, w) || words_overlap(digits, w * n_digits, out1, w))
+        return fail(OFHE_ERR_ARG, "digits overlaps an output");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    return bv_inner_run(p, towers, n_digits, digits, key_b, key_a, key_towers, nullptr, nullptr, out0, out1, batch,
+                        pick(stream));
+}
+
+// KeySwitchInPlace (keyswitch-bv.cpp:283-300) in one call: out0 = add0 + ct0,
+// out1 = add1 + ct1, the decomposition and the inner product run chunk by chunk
+// over a digit scratch of `chunk` digits; every chunk after the first adds into
+// the outputs (the accumulate mode of k_bv_inner_digits).
+int ofhe_hip_bv_key_switch(ofhe_plan_t p, uint32_t towers, uint32_t digit_size, const uint64_t* c,
+                           const uint64_t* key_b, const uint64_t* key_a, uint32_t key_towers, const uint64_t* add0,
+                           const uint64_t* add1, uint64_t* out0, uint64_t* out1, uint32_t chunk_digits, uint32_t batch,
+                           void* stream) {
+    if (!c || !key_b || !key_a || !out0 || !out1 || batch == 0) return fail(OFHE_ERR_ARG, "bad data argument");
+    if (!bv_aligned({c, key_b, key_a, add0, add1, out0, out1}))
+        return fail(OFHE_ERR_ARG, "buffers must be 16-byte aligned");
+    if (digit_size > 30) return fail(OFHE_ERR_ARG, BV_DIGIT_SIZE_MSG);
+    if (key_towers < towers) return fail(OFHE_ERR_ARG, "key_towers smaller than towers");
+    if (out0 == out1) return fail(OFHE_ERR_ARG, "out0 and out1 must be distinct buffers");
+    RCCHK(bv_plan_check(p, towers));
+    const u32 log_n = p->log_n, nd = bv_digits(p->q.data(), towers, digit_size);
+    const u64 TN = (u64)towers << log_n, w = (u64)batch * TN, kw = (u64)nd * key_towers << log_n;
+    RCCHK(outputs_apart(out0, out1, w));
+    u64* const outs[2] = {out0, out1};
+    for (u64* o : outs) {
+        // c is consumed (its INTT) before anything is written: an output may be c itself
+        if (o != c && words_overlap(o, w, c, w)) return fail(OFHE_ERR_ARG, "an output overlaps c without starting at its address");
+        if (words_overlap(o, w, key_b, kw) || words_overlap(o, w, key_a, kw))
+            return fail(OFHE_ERR_ARG, "outputs must not alias the keys");
+    }
+    // an addend is read by the thread that writes the same word of its output, in the first chunk only
+    if ((add0 && add0 != out0 && words_overlap(add0, w, out0, w)) || (add1 && add1 != out1 && words_overlap(add1, w, out1, w)) ||
+        (add0 && words_overlap(add0, w, out1, w)) || (add1 && words_overlap(add1, w, out0, w)))
+        return fail(OFHE_ERR_ARG, "an addend may alias only its own output (add0 == out0, add1 == out1)");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t s = pick(stream);
+    u32 chunk = chunk_digits;
+    if (chunk == 0) chunk = (u32)std::max<u64>(1, BV_CHUNK_SCRATCH_BYTES / (w * 8));
+    chunk = std::min(chunk, nd);
+    Scratch sc, sd;  // c in coefficient form; one chunk of digits
+    RCCHK(sc.alloc((size_t)w * 8, s, p->ctx));
+    RCCHK(sd.alloc((size_t)w * chunk * 8, s, p->ctx));
+    RCCHK(plan_ntt_range(p, true, 0, towers, c, sc.w(), TN, TN, batch, s));
+    const u64 kstep = (u64)key_towers << log_n;
+    for (u32 d0 = 0; d0 < nd; d0 += chunk) {
+        const u32 d1 = std::min(nd, d0 + chunk);
+        RCCHK(bv_decompose_range(p, towers, digit_size, sc.w(), d0, d1, sd.w(), batch, s));
+        RCCHK(bv_inner_run(p, towers, d1 - d0, sd.w(), key_b + d0 * kstep, key_a + d0 * kstep, key_towers,
+                           d0 ? out0 : add0, d0 ? out1 : add1, out0, out1, batch, s));
+    }
+    return OFHE_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -539,6 +539,108 @@ __global__ __launch_bounds__(256) void k_bv_inner(BvArgs A, u32 bpr) {
     st_s(A.o1 + o, barrett128(l1, h1, q, ml, mh));
 }
 
+// PolyImpl::BaseDecompose (poly-impl.h:516-542) for CRTDecompose(r), r > 0
+// (dcrtpoly-impl.h:290-320): windows j0 .. j0 + nw - 1 of one source tower's
+// coefficients, win_j[x] = (coef[x] >> (j r)) & (2^r - 1), written as rows
+// [batch][nw][N].  One thread per (batch entry, coefficient pair): the pair is
+// loaded once and every window of it stored (16-byte accesses); j r < 60 for
+// every window of a modulus below 2^60, so the shifts are defined.
+struct BvWinArgs {
+    const u64* coef;  // [batch] rows of N (stride cstride): the source tower, coefficient form
+    u64 cstride;
+    u64* win;         // [batch][nw][N]
+    u32 r, j0, nw, log_n;
+};
+__global__ __launch_bounds__(256) void k_bv_windows(BvWinArgs A, u32 bpr) {
+    OFHE_VGPR_FLOOR();
+    const u32 b = blockIdx.x / bpr;
+    const u64 N = 1ull << A.log_n;
+    const u64 j = 2 * ((u64)(blockIdx.x % bpr) * blockDim.x + threadIdx.x);
+    if (j >= N) return;
+    const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(A.coef + b * A.cstride + j);
+    const u64 mask = (1ull << A.r) - 1;
+    u64* w = A.win + (u64)b * A.nw * N + j;
+    for (u32 k = 0; k < A.nw; k++) {
+        const u32 sh = (A.j0 + k) * A.r;
+        st2_s(w + (u64)k * N, u64x2{(v.x >> sh) & mask, (v.y >> sh) & mask});
+    }
+}
+
+// EvalFastKeySwitchCore over any number of digits (digitSize > 0: nd is the
+// number of windows, not of towers) and KeySwitchInPlace's additions
+// (keyswitch-bv.cpp:283-300): o = acc + sum_i key[i] . d_i, acc canonical and
+// laid out as o (possibly o itself) or NULL for zero.  acc enters the 128-bit
+// sum before the one reduction; the sum is folded to its residue every
+// BV_FOLD terms (a residue and 256 products of words below 2^60 stay below
+// 2^128), so nd is unbounded and the canonical result does not depend on the
+// grouping.  NB > 1 keeps the key words stationary: a thread holds the
+// accumulators of NB consecutive batch entries and loads each (key_b, key_a)
+// word pair once for all of them.
+constexpr u32 BV_FOLD = 256;
+struct BvDigitArgs {
+    BvArgs a;
+    const u64* acc0;  // [batch][towers][N] or NULL
+    const u64* acc1;
+    u32 batch;
+};
+template <int NB>
+__global__ __launch_bounds__(256) void k_bv_inner_digits(BvDigitArgs D, u32 bpr) {
+    OFHE_VGPR_FLOOR();
+    const BvArgs& A = D.a;
+    const u32 row = blockIdx.x / bpr, g = row / A.towers, t = row % A.towers;
+    const u64 N = 1ull << A.log_n;
+    const u64 j = (u64)(blockIdx.x % bpr) * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const u32 b0 = g * NB;
+    const u32 nb = D.batch - b0 < (u32)NB ? D.batch - b0 : (u32)NB;  // the last group may be short
+    const u64 dstep = (u64)A.towers * N, kstep = (u64)A.key_towers * N, bstep = (u64)A.nd * dstep;
+    const u64 o = (u64)b0 * dstep + (u64)t * N + j;
+    const u64* dp = A.d + (u64)b0 * bstep + (u64)t * N + j;
+    const u64* bp = A.kb + (u64)t * N + j;
+    const u64* ap = A.ka + (u64)t * N + j;
+    const u64 q = A.mu[3 * t], ml = A.mu[3 * t + 1], mh = A.mu[3 * t + 2];
+    u64 l0[NB], h0[NB], l1[NB], h1[NB];
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        const bool on = (u32)k < nb;
+        l0[k] = on && D.acc0 ? ld_s(D.acc0 + o + k * dstep) : 0;
+        l1[k] = on && D.acc1 ? ld_s(D.acc1 + o + k * dstep) : 0;
+        h0[k] = h1[k] = 0;
+    }
+    for (u32 i0 = 0; i0 < A.nd; i0 += BV_FOLD) {
+        const u32 i1 = A.nd - i0 < BV_FOLD ? A.nd : i0 + BV_FOLD;
+        if (i0) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+                l0[k] = barrett128(l0[k], h0[k], q, ml, mh);
+                l1[k] = barrett128(l1[k], h1[k], q, ml, mh);
+                h0[k] = h1[k] = 0;
+            }
+        }
+        for (u32 i = i0; i < i1; i++) {
+            const u64 kbv = bp[i * kstep], kav = ap[i * kstep];
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+                if ((u32)k >= nb) break;
+                const u64 dv = ld_s(dp + k * bstep + i * dstep);
+                u64 lo, hi;
+                mul128(kbv, dv, lo, hi);
+                l0[k] += lo;
+                h0[k] += hi + (l0[k] < lo);
+                mul128(kav, dv, lo, hi);
+                l1[k] += lo;
+                h1[k] += hi + (l1[k] < lo);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        if ((u32)k >= nb) break;
+        st_s(A.o0 + o + k * dstep, barrett128(l0[k], h0[k], q, ml, mh));
+        st_s(A.o1 + o + k * dstep, barrett128(l1[k], h1[k], q, ml, mh));
+    }
+}
+
 // PolyImpl::AutomorphismTransform(k) (poly-impl.h:338-364).  One thread per
 // index j of one (batch, tower) row:
 //   evaluation form:  dst[rev(j)] = src[rev(((k (2j+1)) >> 1) mod n)]

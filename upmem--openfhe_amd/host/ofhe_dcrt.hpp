@@ -1580,6 +1580,119 @@ public:
     static void erase(const std::string& id) { NamedStore<Key>::erase(id); }
 };
 
+// KeySwitchBV (pke/lib/keyswitch/keyswitch-bv.cpp) for one parameter set: Q
+// (element params) and digitSize (CryptoParametersRNS::GetDigitSize(); 0: one
+// digit per tower, r > 0: base-2^r digits, DCRTPolyImpl::CRTDecompose(r)).  An
+// evaluation key is held as KeySwitchHybrid holds its keys: one DCRTPolyHip per
+// half (EvalKeyRelin's b and a vectors) over Q, whose batch index is the digit.
+class KeySwitchBV {
+public:
+    typedef KeyCache::Key Key;
+    // EvalKeySwitchPrecomputeCore's digits, kept on the device: `batch` entries of n_digits polynomials
+    struct Digits {
+        DCRTPolyHip poly;  // [batch][n_digits] polynomials over the level's towers, EVALUATION form
+        uint32_t n_digits, batch;
+    };
+
+    KeySwitchBV(std::shared_ptr<DCRTParams> Q, uint32_t digitSize) : Q_(std::move(Q)), r_(digitSize) {
+        if (r_ > kMaxDigitSize) throw math_error("KeySwitchBV: digitSize must be at most 30");
+    }
+    uint32_t GetDigitSize() const { return r_; }
+
+    // CRTDecompose(digitSize)'s nWindows over the first `towers` of `moduli`; no device
+    static uint32_t DigitCount(const std::vector<uint64_t>& moduli, size_t towers, uint32_t digitSize) {
+        if (digitSize > kMaxDigitSize) throw math_error("DigitCount: digitSize must be at most 30");
+        if (towers < 1 || towers > moduli.size()) throw math_error("DigitCount: towers must be in [1, moduli]");
+        uint32_t n = 0;
+        for (size_t i = 0; i < towers; i++) {
+            uint32_t bits = 0;
+            for (uint64_t q = moduli[i]; q; q >>= 1) bits++;
+            n += digitSize ? (bits + digitSize - 1) / digitSize : 1;
+        }
+        return n;
+    }
+
+    // EvalKeySwitchPrecomputeCore (keyswitch-bv.cpp:308-312): c over Ql (its params give the level)
+    Digits EvalKeySwitchPrecomputeCore(const DCRTPolyHip& c) const {
+        const uint32_t l = level("EvalKeySwitchPrecomputeCore", c);
+        const uint32_t nd = DigitCount(Q_->Moduli(), l, r_);
+        Digits d{DCRTPolyHip::result(c.GetParams(), Format::EVALUATION, c.Batch() * nd), nd, c.Batch()};
+        check(ofhe_hip_bv_precompute_digits(Q_->plan(), l, r_, c.data(), d.poly.data(), c.Batch(), nullptr),
+              "EvalKeySwitchPrecomputeCore");
+        return d;
+    }
+
+    // EvalFastKeySwitchCore (keyswitch-bv.cpp:314-338): (ct0, ct1) over paramsQl, the key cut to its towers
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalFastKeySwitchCore(const Digits& digits, const Key& key,
+                                                              const std::shared_ptr<DCRTParams>& paramsQl) const {
+        check_form(digits.poly, Format::EVALUATION, "EvalFastKeySwitchCore");
+        check_over(digits.poly, *paramsQl, "EvalFastKeySwitchCore", ": the digits are over another basis than paramsQl");
+        const uint32_t l = level("EvalFastKeySwitchCore", digits.poly);
+        if (!digits.n_digits || digits.poly.Batch() != digits.batch * digits.n_digits)
+            throw math_error("EvalFastKeySwitchCore: batch * n_digits digit polynomials expected");
+        check_key("EvalFastKeySwitchCore", key, digits.n_digits);
+        auto o = DCRTPolyHip::result_pair(paramsQl, Format::EVALUATION, digits.batch);
+        check(ofhe_hip_bv_core_digits(Q_->plan(), l, digits.n_digits, digits.poly.data(), key.b.data(), key.a.data(),
+                                      (uint32_t)Q_->Towers(), o.first.data(), o.second.data(), digits.batch, nullptr),
+              "EvalFastKeySwitchCore");
+        return o;
+    }
+
+    // KeySwitchCore (keyswitch-bv.cpp:302-306), the digits produced and consumed in chunks on the device
+    std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchCore(const DCRTPolyHip& c, const Key& key) const {
+        const uint32_t l = level("KeySwitchCore", c);
+        check_key("KeySwitchCore", key, DigitCount(Q_->Moduli(), l, r_));
+        auto o = DCRTPolyHip::result_pair(c.GetParams(), Format::EVALUATION, c.Batch());
+        run("KeySwitchCore", l, c, key, nullptr, nullptr, o.first, o.second);
+        return o;
+    }
+
+    // KeySwitchInPlace (keyswitch-bv.cpp:283-300) on the elements of a ciphertext: c0 += ct0, and c1 = ct1
+    // (two elements) or c1 += ct1 with the third element dropped (three)
+    void KeySwitchInPlace(std::vector<DCRTPolyHip>& cv, const Key& key) const {
+        if (cv.size() != 2 && cv.size() != 3) throw math_error("KeySwitchInPlace: 2 or 3 ciphertext elements expected");
+        const DCRTPolyHip& c = cv.back();
+        const uint32_t l = level("KeySwitchInPlace", c);
+        for (const DCRTPolyHip& e : cv) {
+            check_form(e, Format::EVALUATION, "KeySwitchInPlace");
+            if (e.GetParams()->Moduli() != c.GetParams()->Moduli() || e.Batch() != c.Batch())
+                throw math_error("KeySwitchInPlace: elements over one basis and of one batch expected");
+        }
+        check_key("KeySwitchInPlace", key, DigitCount(Q_->Moduli(), l, r_));
+        // two elements: c1 is both the input and, once consumed, the output
+        run("KeySwitchInPlace", l, c, key, &cv[0], cv.size() == 3 ? &cv[1] : nullptr, cv[0], cv[1]);
+        if (cv.size() == 3) cv.pop_back();
+    }
+
+private:
+    static constexpr uint32_t kMaxDigitSize = 30;  // the reference forms 1 << digitSize in an int
+    uint32_t level(const char* op, const DCRTPolyHip& c) const {
+        check_form(c, Format::EVALUATION, op);
+        const size_t l = c.GetParams()->Towers();
+        if (l > Q_->Towers()) throw math_error(std::string(op) + ": ciphertext has more towers than Q");
+        if (c.GetParams()->LogN() != Q_->LogN() || c.GetParams()->Moduli() != towers_of(Q_->Moduli(), 0, l))
+            throw math_error(std::string(op) + ": the polynomial is not over the first towers of Q");
+        return (uint32_t)l;
+    }
+    void check_key(const char* op, const Key& key, uint32_t n_digits) const {
+        check_over(key.b, *Q_, op, ": evaluation key must be polynomials over Q");
+        check_over(key.a, *Q_, op, ": evaluation key must be polynomials over Q");
+        check_form(key.b, Format::EVALUATION, op);
+        check_form(key.a, Format::EVALUATION, op);
+        if (key.b.Batch() < n_digits || key.a.Batch() < n_digits)
+            throw math_error(std::string(op) + ": evaluation key has fewer polynomials than the level has digits");
+    }
+    void run(const char* op, uint32_t l, const DCRTPolyHip& c, const Key& key, const DCRTPolyHip* add0,
+             const DCRTPolyHip* add1, DCRTPolyHip& out0, DCRTPolyHip& out1) const {
+        check(ofhe_hip_bv_key_switch(Q_->plan(), l, r_, c.data(), key.b.data(), key.a.data(), (uint32_t)Q_->Towers(),
+                                     add0 ? add0->data() : nullptr, add1 ? add1->data() : nullptr, out0.data(),
+                                     out1.data(), 0, c.Batch(), nullptr),
+              op);
+    }
+    std::shared_ptr<DCRTParams> Q_;
+    uint32_t r_;
+};
+
 inline std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchHybrid::LinearTransform(const DCRTPolyHip& c0,
                                                                             const DCRTPolyHip& c1,
                                                                             const BsgsPlan& plan,

@@ -185,6 +185,14 @@ _SIGS = {
     "ofhe_hip_bv_precompute": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_bv_core": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp,
                                         ctypes.c_uint32, _vp]),
+    "ofhe_hip_bv_digit_count": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bv_precompute_digits": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                     _vp]),
+    "ofhe_hip_bv_core_digits": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
+                                               _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bv_key_switch": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
+                                              _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bv_tune": (ctypes.c_int, [ctypes.c_uint32]),
     "ofhe_hip_eval_mult_core": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_switch_crt_basis": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_expand_crt_basis": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp]),
@@ -271,6 +279,20 @@ def _ptrs(v):
 
 def version() -> str:
     return lib().ofhe_hip_version().decode()
+
+
+def bv_digit_count(moduli: Sequence[int], digit_size: int) -> int:
+    """CRTDecompose(digit_size)'s nWindows over `moduli` (dcrtpoly-impl.h:290-300), with no device: one digit
+    per tower at 0, else ceil(bitlen(q_i) / digit_size) windows per tower."""
+    r = int(digit_size)
+    if not 0 <= r <= 30:
+        raise MathError("digit_size must be at most 30 (the reference forms 1 << digitSize in an int)")
+    return sum(-(-int(q).bit_length() // r) if r else 1 for q in moduli)
+
+
+def bv_tune(key_stationary: int) -> None:
+    """ofhe_hip_bv_tune: batch entries per thread of the BV inner product (0 auto, 1 plain, 2, 4)."""
+    _check(lib().ofhe_hip_bv_tune(int(key_stationary)))
 
 
 def device_count() -> int:
@@ -524,6 +546,34 @@ class NTTPlan(_Handle):
         """EvalFastKeySwitchCore: out0 = sum_i kb[i] d_i, out1 = sum_i ka[i] d_i."""
         _check(lib().ofhe_hip_bv_core(self.handle, int(towers), _vp(digits), _vp(key_b), _vp(key_a), int(key_towers),
                                       _vp(out0), _vp(out1), int(batch), _vp(stream or None)))
+
+    # --- BV key switching with a digit size (CRTDecompose(r), dcrtpoly-impl.h:266-320); 0 = the calls above ---
+    def bv_digit_count(self, towers: int, digit_size: int) -> int:
+        """The reference's nWindows over the plan's first `towers` moduli."""
+        n = ctypes.c_uint32(0)
+        _check(lib().ofhe_hip_bv_digit_count(self.handle, int(towers), int(digit_size), ctypes.byref(n)))
+        return n.value
+
+    def bv_precompute_digits(self, towers: int, digit_size: int, c: int, digits: int, batch: int = 1,
+                             stream: int = 0) -> None:
+        """CRTDecompose(digit_size) of c [batch][towers][N] (evaluation form) -> digits [batch][n_digits][towers][N]."""
+        _check(lib().ofhe_hip_bv_precompute_digits(self.handle, int(towers), int(digit_size), _vp(c), _vp(digits),
+                                                   int(batch), _vp(stream or None)))
+
+    def bv_core_digits(self, towers: int, n_digits: int, digits: int, key_b: int, key_a: int, key_towers: int,
+                       out0: int, out1: int, batch: int = 1, stream: int = 0) -> None:
+        """EvalFastKeySwitchCore over n_digits digits and the first n_digits polynomials of the keys."""
+        _check(lib().ofhe_hip_bv_core_digits(self.handle, int(towers), int(n_digits), _vp(digits), _vp(key_b),
+                                             _vp(key_a), int(key_towers), _vp(out0), _vp(out1), int(batch),
+                                             _vp(stream or None)))
+
+    def bv_key_switch(self, towers: int, digit_size: int, c: int, key_b: int, key_a: int, key_towers: int, add0: int,
+                      add1: int, out0: int, out1: int, chunk_digits: int = 0, batch: int = 1, stream: int = 0) -> None:
+        """KeySwitchInPlace: out0 = add0 + ct0, out1 = add1 + ct1 (an addend of 0 / None is zero), the digits
+        produced and consumed chunk_digits at a time (0: the library's scratch bound)."""
+        _check(lib().ofhe_hip_bv_key_switch(self.handle, int(towers), int(digit_size), _vp(c), _vp(key_b), _vp(key_a),
+                                            int(key_towers), _vp(add0 or None), _vp(add1 or None), _vp(out0),
+                                            _vp(out1), int(chunk_digits), int(batch), _vp(stream or None)))
 
     # --- LeveledSHEBase::EvalMultCore, 2 x 2 elements (base-leveledshe.cpp:667-672) ---
     def eval_mult_core(self, c0: int, c1: int, d0: int, d1: int, out0: int, out1: int, out2: int, batch: int = 1,
