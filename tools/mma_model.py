@@ -133,7 +133,9 @@ def main():
 # Round 6: the pipeline-wide matrix-core budget.  Inputs are measurements,
 # each with its record:
 #   * k_block (butterflies), k_tcols fwd / inv: SQ_INSTS_VALU per coefficient,
-#     profiles/pmc_current.json (r05y, the shipped build): 180.75 / 80.1 / 95.1
+#     profiles/pmc_current.json as of r05y (the build shipped then): 180.75 / 80.1 / 95.1.
+#     The column passes have since moved to two columns per thread (72.1 / 83.25 today);
+#     the model keeps the build its other inputs (HEADLINE, the issue rates) were measured on.
 #   * k_block_m16 (round 3, 4 MFMA rounds): 172.0 per coefficient measured
 #     (profiles/r03_block_m16_pmc/), issue 0.121 wave-instr per SIMD-cycle;
 #     its loop body, recompiled from 2ae2740 (ntt_m16.hpp) and counted by

@@ -23,7 +23,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 NAMES = {"k_block<2,": "k_block<fused>", "k_tcols<false": "colpass<fwd>", "k_tcols<true": "colpass<inv>",
-         "k_cols<4, false": "colpass<fwd>", "k_cols<4, true": "colpass<inv>"}
+         "k_tcols_inv2<": "colpass<inv>", "k_cols<4, false": "colpass<fwd>", "k_cols<4, true": "colpass<inv>"}
 
 
 def kname(n):

@@ -11,7 +11,7 @@ import sys
 
 d = sys.argv[1]
 NAMES = {"k_block<2,": "k_block<fused>", "k_tcols<false": "colpass<fwd>", "k_tcols<true": "colpass<inv>",
-         "k_cols<4, false": "colpass<fwd>", "k_cols<4, true": "colpass<inv>"}
+         "k_tcols_inv2<": "colpass<inv>", "k_cols<4, false": "colpass<fwd>", "k_cols<4, true": "colpass<inv>"}
 out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) on bench.py --steps 2",
        "correction": "hbm_bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE halving)",
        "kernels": {}}

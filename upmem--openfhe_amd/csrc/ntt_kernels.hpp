@@ -450,6 +450,30 @@ __device__ __forceinline__ void fwd_round16_canon(u64 (&v)[Q][16], const u64* tw
     fwd_stage16<2>(v, tw, M0, M);
     fwd_stage16<3>(v, tw, M0, M);
 }
+// one b8[16] for all sets: a register's bound depends on its position only
+template <int S, int Q, class M_>
+__device__ __forceinline__ void inv_stage16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = itw + 2 * ((u64)M0 << S);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base, j);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++) {
+#pragma unroll
+            for (int c = 0; c < Q; c++) gs_bfly_b(v[c][k], v[c][k + half], w, M, b8[k] || b8[k + half]);
+            b8[k] = true;
+            b8[k + half] = false;
+        }
+    }
+}
+template <int Q, class M_>
+__device__ __forceinline__ void inv_round16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
+    inv_stage16_b<3>(v, b8, itw, M0, M);
+    inv_stage16_b<2>(v, b8, itw, M0, M);
+    inv_stage16_b<1>(v, b8, itw, M0, M);
+    inv_stage16_b<0>(v, b8, itw, M0, M);
+}
 template <int S, int Q, class M_>
 __device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[Q][16], const u64* tw3, u32 U, u32 u, const M_& M) {
     constexpr int half = 8 >> S;
@@ -1017,8 +1041,7 @@ static_assert(TCOLS_CPT == 1 || TCOLS_W == 16, "two columns per thread: 16 colum
 // columns.  The two column sets go through the CPT = 1 tile (same patterns,
 // same padding) one after the other, so the kernel keeps 34 816 bytes of LDS
 // and four workgroups per CU.  Per column the operations and their order are
-// those of the CPT = 1 body.  The inverse pass stays at one column per thread
-// (rejected variants).
+// those of the CPT = 1 body.  tcols_pairs_inv below is the inverse pass's form.
 template <bool SPQ>
 __device__ __forceinline__ void tcols_pairs_fwd(const PlanArgs& P, const u64* src, u64* dst, u32 batch, u32 wid,
                                                 u64* lds, u32 tid) {
@@ -1055,6 +1078,150 @@ __device__ __forceinline__ void tcols_pairs_fwd(const PlanArgs& P, const u64* sr
     fwd_round16(v, tw, 16 + h, M);
 #pragma unroll
     for (int k = 0; k < 16; k++) st2_s(y + (u64)(16 * h + k) * S, u64x2{v[0][k], v[1][k]});
+}
+#ifndef OFHE_TCOLS_CPT_INV
+#define OFHE_TCOLS_CPT_INV 2  // columns per thread of the inverse pass at N = 2^16: 1 or 2
+#endif
+constexpr int TCOLS_CPT_INV = OFHE_TCOLS_CPT_INV;
+static_assert(TCOLS_CPT_INV == 1 || TCOLS_CPT_INV == 2, "columns per thread");
+static_assert(TCOLS_CPT_INV == 1 || TCOLS_W == 16, "two columns per thread: 16 column pairs per tile row");
+#ifndef OFHE_TCOLS_INV_HOLD
+// Dynamic LDS bytes launch_colpass adds to every k_tcols_inv2 workgroup and the
+// kernel never touches: 34 816 + 14 336 = 49 152 bytes leave room for three
+// workgroups per CU, where the pass runs 7 % faster than at the four its own
+// registers and tile allow.  0: four workgroups per CU.
+#define OFHE_TCOLS_INV_HOLD 14336
+#endif
+constexpr u32 TCOLS_INV_HOLD = OFHE_TCOLS_INV_HOLD;
+// A 16-byte global access at a wave-uniform base plus a 32-bit byte offset per
+// lane (plus an immediate): the address costs no vector instruction.  The
+// empty asm pins the base to scalar registers, so LLVM cannot fold the lane
+// offset into a 64-bit vector pointer.
+typedef __attribute__((address_space(1))) char* gptr;
+typedef __attribute__((address_space(1))) u64x2* gptr2;
+__device__ __forceinline__ gptr sbase(const void* p) {
+    gptr q = (gptr)(p);
+    asm("" : "+s"(q));
+    return q;
+}
+__device__ __forceinline__ Tw ldtw_o(gptr base, u32 off) {
+    const u64x2 v = *(gptr2)(base + off);
+    return Tw{v.x, v.y};
+}
+__device__ __forceinline__ u64x2 ld2_so(gptr base, u32 off) { return __builtin_nontemporal_load((gptr2)(base + off)); }
+__device__ __forceinline__ void st2_so(gptr base, u32 off, u64x2 v) {
+    __builtin_nontemporal_store(v, (gptr2)(base + off));
+}
+// Round 1 of tcols_pairs_inv (rows 16h + k): inv_round16_b on Q register sets
+// whose twiddles differ per lane.  Entry (M0 << S) + j of stage S sits at byte
+// (M0 << S) * 16 + 16 j of itw with M0 = 16 + h, so itw + (16 << S) * 16 bytes
+// is a uniform base, 16 h << S the lane's offset and 16 j an immediate.  The
+// fifteen entries are fetched in groups of at most four (entries J0 .. J0 + G
+// of stage S), at most three groups in registers at a time, each group one
+// group of butterflies ahead of its use; scheduling barriers keep the loads
+// where they are written (all fifteen hoisted are 60 VGPRs).
+template <int S, int J0, int G>
+__device__ __forceinline__ void ld_rows_tw(Tw (&w)[G], const char* itw, u32 h) {
+    const gptr base = sbase(itw + ((16u << S) * 16));
+    const u32 hoff = h << (S + 4);
+#pragma unroll
+    for (int i = 0; i < G; i++) w[i] = ldtw_o(base, hoff + 16 * (J0 + i));
+}
+template <int S, int J0, int G, int Q, class M_>
+__device__ __forceinline__ void inv_bflies_rows(u64 (&v)[Q][16], bool (&b8)[16], const Tw (&w)[G], const M_& M) {
+    constexpr int half = 8 >> S;
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+#pragma unroll
+        for (int k = (J0 + i) * 2 * half; k < (J0 + i) * 2 * half + half; k++) {
+#pragma unroll
+            for (int c = 0; c < Q; c++) gs_bfly_b(v[c][k], v[c][k + half], w[i], M, b8[k] || b8[k + half]);
+            b8[k] = true;
+            b8[k + half] = false;
+        }
+    }
+}
+__device__ __forceinline__ void tw_fence() { __builtin_amdgcn_sched_barrier(0); }
+template <int Q, class M_>
+__device__ __forceinline__ void inv_round16_b_rows(u64 (&v)[Q][16], bool (&b8)[16], const char* itw, u32 h,
+                                                   const M_& M) {
+    // stage S has 2^S entries: 8 (two groups), 4, 2, 1
+    Tw wa[4], wb[4], w1[2], w0[1];
+    // each group is fetched one group of butterflies ahead of its use
+    ld_rows_tw<3, 0>(wa, itw, h);
+    ld_rows_tw<3, 4>(wb, itw, h);
+    tw_fence();
+    inv_bflies_rows<3, 0>(v, b8, wa, M);
+    tw_fence();
+    ld_rows_tw<2, 0>(wa, itw, h);
+    tw_fence();
+    inv_bflies_rows<3, 4>(v, b8, wb, M);
+    tw_fence();
+    ld_rows_tw<1, 0>(w1, itw, h);
+    ld_rows_tw<0, 0>(w0, itw, h);
+    tw_fence();
+    inv_bflies_rows<2, 0>(v, b8, wa, M);
+    inv_bflies_rows<1, 0>(v, b8, w1, M);
+    inv_bflies_rows<0, 0>(v, b8, w0, M);
+}
+// Two columns per thread in the inverse pass (N = 2^16): the mirror of
+// tcols_pairs_fwd.  Thread (h, r) holds v[c][k] of columns 2r + c; round 1
+// (rows 16h + k) fetches each per-lane twiddle once for both columns, round 2
+// (rows h + 16k) each tower-uniform one.  The two sets go through the one-set
+// tile in turn with the inverse's unpadded, conflict-free patterns.  Per
+// column the operations and their order are those of the CPT = 1 body.
+template <bool SPQ>
+__device__ __forceinline__ void tcols_pairs_inv(const PlanArgs& P, const u64* src, u64* dst, u32 batch, u32 wid,
+                                                u64* lds, u32 tid) {
+    constexpr u32 N = 1u << 16, S = 256, W = 16, TILES = S / (2 * W);
+    const u32 cb = wid % TILES;
+    const u32 pb = wid / TILES;
+    const u32 t = pb / batch, b = pb % batch;
+    const u32 h = tid / W, r = tid % W;
+    const u64 tile = (u64)t * N + cb * 2 * W;  // even: 16-byte accesses (launch_colpass checks the rest)
+    const char* x = reinterpret_cast<const char*>(src + (u64)b * P.sstride + tile);
+    char* y = reinterpret_cast<char*>(dst + (u64)b * P.dstride + tile);
+    const u32 xo = h * (16 * S * 8) + r * 16;  // row 16h, columns 2r, 2r + 1
+    const u32 yo = h * (S * 8) + r * 16;       // row h
+    const TowerConst tc = P.tc[t];
+    const Mod<SPQ> M = load_mod<SPQ>(tc);
+    const u64* itw = P.itw + (u64)t * N * 2;
+    u64 v[2][16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const u64x2 e = ld2_so(sbase(x + k * (S * 8)), xo);
+        v[0][k] = e.x;
+        v[1][k] = e.y;
+    }
+    bool b8[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) b8[k] = false;
+    inv_round16_b_rows(v, b8, reinterpret_cast<const char*>(itw), h, M);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        if (c) __syncthreads();  // every thread has read set 0
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[h * 16 * W + r + W * k] = v[c][k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[c][k] = lds[tid + 16 * W * k];
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) b8[k] = true;
+    inv_round16_b(v, b8, itw, 1, M);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const u64x2 e{b8[k] ? canon8m(v[0][k], M) : canon4m(v[0][k], M),
+                      b8[k] ? canon8m(v[1][k], M) : canon4m(v[1][k], M)};
+        st2_so(sbase(y + k * (16 * S * 8)), yo, e);
+    }
+}
+template <bool SPQ>
+__global__ __launch_bounds__(16 * TCOLS_W, OFHE_KB_WAVES) void k_tcols_inv2(PlanArgs P, const u64* src, u64* dst,
+                                                                            u32 batch, u32 nwg) {
+    OFHE_VGPR_FLOOR();
+    __shared__ u64 lds[TCOLS_LDS_WORDS];
+    tcols_pairs_inv<SPQ>(P, src, dst, batch, xcd_remap(blockIdx.x, nwg), lds, threadIdx.x);
 }
 // The body of k_tcols for work item wid (column tile cb = wid % (S / W) of
 // polynomial tower pb = wid / (S / W), W CPT columns per tile) on the caller's

@@ -566,8 +566,19 @@ static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, con
                 // thread (16-byte accesses) when every row segment of src and dst
                 // is 16-byte aligned; any other call runs one column per thread
                 // and gives the same words
-                const bool pairs = TCOLS_CPT == 2 && !inv && split == SPLIT_T8 && !lift &&
-                                   !(((uintptr_t)src | (uintptr_t)dst) & 15) && !((a.sstride | a.dstride) & 1);
+                const bool aligned = split == SPLIT_T8 && !lift && !(((uintptr_t)src | (uintptr_t)dst) & 15) &&
+                                     !((a.sstride | a.dstride) & 1);
+                const bool pairs = TCOLS_CPT == 2 && !inv && aligned;
+                // so does the inverse pass (k_tcols_inv2), under the same conditions, at
+                // three workgroups per CU (TCOLS_INV_HOLD bytes of unused dynamic LDS)
+                if constexpr (INV && !SWS && TCOLS_CPT_INV == 2) {
+                    if (aligned) {
+                        const u32 nwg = polys * (256 / (2 * TCOLS_W));
+                        hipLaunchKernelGGL((k_tcols_inv2<SP>), dim3(nwg), dim3(16 * TCOLS_W), TCOLS_INV_HOLD, s, a, src,
+                                           dst, batch, nwg);
+                        return;
+                    }
+                }
                 with_int<16, 17>(split == SPLIT_T8B9 ? 17 : 16, [&](auto ln) { with_bool(pairs, [&](auto pr) {
                     constexpr int LOGN = decltype(ln)::value;
                     constexpr int CPT = (decltype(pr)::value && !INV && LOGN == 16 && !SWS) ? TCOLS_CPT : 1;
