@@ -952,6 +952,80 @@ int ofhe_hip_bfv_decrypt(ofhe_bfv_decrypt_t handle, ofhe_plan_t plan_q, uint32_t
  * without tInvModq / negQModt. */
 int ofhe_hip_times_q_over_t(ofhe_bfv_decrypt_t handle, const uint64_t* x, uint64_t* out, uint32_t batch, void* stream);
 
+/* ---- BGV decryption and the CKKS / generic decryption core: PKEBGVRNS::Decrypt
+ *      (pke/lib/scheme/bgvrns/bgvrns-pke.cpp:44-99), PKECKKSRNS::Decrypt
+ *      (ckksrns-pke.cpp:44-97) and PKERNS::Decrypt (rns-pke.cpp:70-109), so that
+ *      only the plaintext crosses the bus.  Integers only, bit-exact with the
+ *      reference's NATIVEINT == 64 build.
+ *
+ * The handle builds negtInvModq[j] = q_j - t^-1 mod q_j and qlInvModq[j][i] =
+ * q_j^-1 mod q_i, i < j (bgvrns-cryptoparameters.cpp:91-107), with their
+ * preconditioners, from the moduli, as ofhe_hip_ks_rescale does; create uploads
+ * once and waits (it cannot run under stream capture) and returns OFHE_ERR_ARG
+ * -- before it looks at ctx -- for t < 2, size_q of 0 or above
+ * OFHE_BGV_DECRYPT_MAX_TOWERS, a modulus that is even or not below 2^60, a
+ * repeated modulus (or one not invertible modulo an earlier one), or t not
+ * invertible modulo some q_j, j >= 1 (q_0 is never divided out, so t may share
+ * a factor with it).  Every other call is stream-ordered and never
+ * synchronises. */
+#define OFHE_BGV_DECRYPT_MAX_TOWERS 64
+typedef struct ofhe_bgv_decrypt_s* ofhe_bgv_decrypt_t;
+int ofhe_hip_bgv_decrypt_create(ofhe_ctx_t ctx, uint32_t log_n, uint32_t size_q, const uint64_t* q, uint64_t t,
+                                ofhe_bgv_decrypt_t* handle);
+int ofhe_hip_bgv_decrypt_destroy(ofhe_bgv_decrypt_t handle);
+/* The ModReduce chain Q_l -> q_0 of bgvrns-pke.cpp:55-60 / 74-81 on a
+ * polynomial in coefficient form, x [batch][size_ql][N] over q[0..size_ql) ->
+ * out [batch][N], 1 <= size_ql <= size_q.  Per coefficient, for j = size_ql - 1
+ * down to 1 (DCRTPolyImpl::ModReduce, dcrtpoly-impl.h:792-812):
+ *   delta = x_j negtInvModq[j] mod q_j
+ *   x_i   = (x_i + SwitchModulus(delta, q_j -> q_i) (t mod q_i) mod q_i) qlInvModq[j][i] mod q_i,  i < j
+ * with SwitchModulus as ofhe_hip_switch_modulus (mubintvecnat.cpp:111-136).
+ * to_plaintext == 0: out is x_0, canonical mod q_0.  Otherwise out is
+ * NativeVectorT::Mod(t) of it (mubintvecnat.cpp:139-166), which is
+ * PolyImpl::DecryptionCRTInterpolate (poly-impl.h:566-575) on one tower:
+ * 1 & (x ^ (x > q_0 >> 1)) for t == 2 (ModByTwoEq, :379-384); x + (t - q_0) above
+ * q_0 >> 1 for t > q_0; else x + (t - q_0 mod t) above q_0 >> 1, then % t when
+ * >= t.  size_ql == 1 is the ending alone.  One kernel launch per 8 towers
+ * retired, one thread per (batch entry, coefficient): (size_ql + 1) * 8 bytes
+ * move per coefficient up to 9 towers.  out may not overlap x; buffers are
+ * 16-byte aligned; scratch (past 9 towers) comes from the context's
+ * stream-ordered pool. */
+int ofhe_hip_bgv_mod_reduce_chain(ofhe_bgv_decrypt_t handle, uint32_t size_ql, int to_plaintext, const uint64_t* x,
+                                  uint64_t* out, uint32_t batch, void* stream);
+/* PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) of `elements` (2 or 3) ciphertext
+ * elements c0, c1 (, c2), each [batch][size_ql][N] over q[0..size_ql), and the
+ * secret key s [size_q][N] in evaluation form over the full chain, shared by
+ * the batch; its first size_ql towers are what DecryptCore's DropLastElements
+ * leaves (rns-pke.cpp:199-224).  out [batch][N], words mod t.  The reference's
+ * two branches produce different intermediate words and both are kept:
+ *   eval_form != 0 (:52-60): one launch forms b = c0 + c1 s (+ c2 s^2) on
+ *     size_ql towers, INTT of those towers, the chain with to_plaintext;
+ *   eval_form == 0 (:72-93): the chain without the ending on each element,
+ *     then DecryptCore on tower 0 alone (forward NTT of the reduced elements,
+ *     the product with s_0, INTT), then Mod t.
+ * plan_q must transform exactly the handle's towers at its N in its context.
+ * The scaling factor the reference returns is host arithmetic on the caller's
+ * factors (bgvrns-pke.cpp:62-69, 82-89) and stays with the caller. */
+int ofhe_hip_bgv_decrypt(ofhe_bgv_decrypt_t handle, ofhe_plan_t plan_q, uint32_t size_ql, uint32_t elements,
+                         int eval_form, const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* s,
+                         uint64_t* out, uint32_t batch, void* stream);
+/* PKERNS::DecryptCore (rns-pke.cpp:199-224) over the first size_ql towers of
+ * plan: b = c0 + c1 s (+ c2 s^2), elements [batch][size_ql][N] all in
+ * evaluation form (eval_form != 0) or all in coefficient form (transformed
+ * first, as the reference does), s [>= size_ql][N] in evaluation form.
+ * coeff_out != 0 adds b.SetFormat(COEFFICIENT) on all size_ql towers, which is
+ * PKECKKSRNS::Decrypt (ckksrns-pke.cpp:44-97) and PKERNS::Decrypt (rns-pke.cpp:
+ * 70-109) up to their last line: for size_ql == 1 out is the NativePoly; for
+ * more towers the caller's CRTInterpolate of out stays on the host (big
+ * integers are out of scope).  CKKS noise flooding (ckksrns-pke.cpp:49-54) is
+ * sampling and stays with the caller: coeff_out == 0 returns b in evaluation
+ * form for it to add to.  out [batch][size_ql][N] may be c0 itself; any other
+ * overlap is refused.  The first call on a plan uploads q and floor(2^128 / q)
+ * and waits; later calls never synchronise. */
+int ofhe_hip_decrypt_core(ofhe_plan_t plan, uint32_t size_ql, uint32_t elements, int eval_form, int coeff_out,
+                          const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* s, uint64_t* out,
+                          uint32_t batch, void* stream);
+
 /* ---- multi-GPU: evaluation-key broadcast over RCCL (xGMI) ----
  * the path shards by ciphertext batch with no exchange;
  * the one collective is the broadcast of the key-switching keys from a root

@@ -192,8 +192,9 @@ int ofhe_hip_bfv_decrypt(ofhe_bfv_decrypt_t h, ofhe_plan_t plan_q, uint32_t elem
             cv[k] = e;
         }
     with_bool(elements == 3, [&](auto three) {
-        hipLaunchKernelGGL((k_decrypt_core<decltype(three)::value>), g, dim3(256), 0, st, h->args, cv[0], cv[1], cv[2],
-                           s, b, one);
+        hipLaunchKernelGGL((k_decrypt_core<decltype(three)::value>), g, dim3(256), 0, st,
+                           CoreArgs{h->args.qv, h->args.qmu, h->args.log_n, h->args.size_q}, cv[0], cv[1], cv[2], s, b,
+                           one);
     });
     RCCHK(post_launch());
     // b.SetFormat(COEFFICIENT) (bfvrns-pke.cpp:211)

@@ -6,7 +6,7 @@
 //   DCRTPolyImpl::ScaleAndRound -> NativePoly, BEHZ         dcrtpoly-impl.h:2005-2049
 //   NativeVectorT::MultiplyAndRound + SwitchModulus (one tower)
 //                                 mubintvecnat.cpp:420-435, ubintnat.h:536-540, bfvrns-pke.cpp:233-245
-//   PKERNS::DecryptCore                                     rns-pke.cpp:199-224
+//   PKERNS::DecryptCore                                     rns-pke.cpp:199-224 (k_decrypt_core, bgv_decrypt_kernels.hpp)
 //   DCRTPolyImpl::TimesQovert                               dcrtpoly-impl.h:1015-1031
 //
 // Floating-point contract (that of bfv_kernels.hpp: the reference uses double
@@ -30,6 +30,7 @@
 //     correctly rounded IEEE division (fp_div), multiply and add separate.
 #pragma once
 #include "bfv_kernels.hpp"
+#include "bgv_decrypt_kernels.hpp"
 #include "ntt_kernels.hpp"
 
 namespace ofhe {
@@ -59,7 +60,7 @@ struct DecArgs {
     const u64* wb;        // [size_q][2]  HPS: tQHatInvModqBDivqModt, precon mod t; BEHZ: negInvqModtgamma, precon mod tgamma
     const double* frac;   // [size_q]     tQHatInvModqDivqFrac
     const double* fracb;  // [size_q]     tQHatInvModqBDivqFrac
-    const u64* qmu;       // [size_q][2]  floor(2^128 / q_i)   (DecryptCore)
+    const u64* qmu;       // [size_q][2]  floor(2^128 / q_i)   (DecryptCore: CoreArgs)
     const u64* tiq;       // [size_q][2]  tInvModq, precon mod q_i (TimesQovert)
     u64 t, tgamma, nqt, nqt_pre;  // NegQModt and its precon mod t
     double td, tinv;
@@ -188,33 +189,6 @@ __global__ __launch_bounds__(256) void k_dec_one_tower(DecArgs A, const u64* __r
             if (r >= q) r = umod64(r, q);
         }
         st_s(out + gid, switch_mod1(r, A.sw));
-    }
-}
-
-// ---------------------------------------------------------------------------
-// DecryptCore: b = c0 + c1 s (+ c2 s^2), towerwise, canonical.  c*: [batch]
-// [size_q][N], s: [size_q][N], all in evaluation form; one thread per word.
-// ---------------------------------------------------------------------------
-template <bool THREE>
-__global__ __launch_bounds__(256) void k_decrypt_core(DecArgs A, const u64* __restrict__ c0, const u64* __restrict__ c1,
-                                                      const u64* __restrict__ c2, const u64* __restrict__ s,
-                                                      u64* __restrict__ out, u64 total) {
-    OFHE_VGPR_FLOOR();
-    const u64 step = (u64)gridDim.x * blockDim.x;
-    for (u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x; gid < total; gid += step) {
-        const u32 row = (u32)(gid >> A.log_n), i = row % A.size_q;
-        const u64 q = A.qv[i], m0 = A.qmu[2 * i], m1 = A.qmu[2 * i + 1];
-        const u64 sv = s[((u64)i << A.log_n) + (gid & ((1ull << A.log_n) - 1))];
-        u64 lo, hi;
-        mul128(ld_s(c1 + gid), sv, lo, hi);
-        u64 acc = csub(ld_s(c0 + gid) + barrett128(lo, hi, q, m0, m1), q);
-        if (THREE) {
-            mul128(sv, sv, lo, hi);
-            const u64 s2 = barrett128(lo, hi, q, m0, m1);
-            mul128(ld_s(c2 + gid), s2, lo, hi);
-            acc = csub(acc + barrett128(lo, hi, q, m0, m1), q);
-        }
-        st_s(out + gid, acc);
     }
 }
 

@@ -1,6 +1,6 @@
 // compose.hpp -- the host skeleton shared by the translation units that
 // compose kernels into BFV-family operations (keyswitch.hip, bfv.hip,
-// bfv_leveled.hip, behz.hip, bfv_decrypt.hip): argument checks, handle
+// bfv_leveled.hip, behz.hip, bfv_decrypt.hip, bgv_decrypt.hip): argument checks, handle
 // boilerplate, launch grids and the launch sequences they have in common.
 // Host code only, with internal linkage: nothing here is part of the C ABI or
 // adds to the library's exported symbols.

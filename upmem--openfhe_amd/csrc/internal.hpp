@@ -6,7 +6,8 @@
 // ScaleAndRound, BFV multiplication (HPS, HPSPOVERQ); bfv_leveled.hip:
 // HPSPOVERQLEVELED multiplication and relinearisation with dropped levels;
 // behz.hip: BFV multiplication (BEHZ); bfv_decrypt.hip: BFV decryption,
-// TimesQovert; comm.hip: multi-device collectives).  compose.hpp, on top of
+// TimesQovert; bgv_decrypt.hip: BGV decryption, DecryptCore; comm.hip:
+// multi-device collectives).  compose.hpp, on top of
 // this header, holds the host code those files share when they compose kernels.
 // Not part of the C ABI.
 #pragma once

@@ -30,6 +30,11 @@
 //                                (bfvrns-leveledshe.cpp:235-274, 367-382, 459-499,
 //                                845-899, dcrtpoly-impl.h:1514-1534) and
 //                                FindLevelsToDrop (bfvrns-leveledshe.cpp:77-166)
+//   DecryptCore, BgvDecrypt / BgvDecryptCache
+//                             <- PKERNS::DecryptCore (rns-pke.cpp:199-224), with
+//                                coeff_out PKECKKSRNS::Decrypt / PKERNS::Decrypt up
+//                                to their last line, and PKEBGVRNS::Decrypt with
+//                                its scalingFactorInt (bgvrns-pke.cpp:44-99)
 //   KsCache / KeyCache        <- the per-parameter-set HYBRID tables
 //                                (rns-cryptoparameters.cpp:72-345) and the
 //                                evaluation keys kept resident on the device
@@ -1203,6 +1208,133 @@ inline void DCRTPolyHip::TimesQovert(const BfvDecrypt& d) {
     check_over(*this, *d.GetParams(), "TimesQovert");
     check(ofhe_hip_times_q_over_t(d.handle(), data(), data(), batch_, nullptr), "TimesQovert");
 }
+
+// The rule DecryptCore and BgvDecrypt::Decrypt share (rns-pke.cpp:199-224): 2
+// or 3 elements of one basis Q_l, one format and one batch, and the secret key
+// in EVALUATION form, batch 1, over a chain whose first towers are Q_l (its
+// DropLastElements).
+inline void check_ciphertext(const std::vector<DCRTPolyHip>& cv, const DCRTPolyHip& s, const char* op) {
+    if (cv.size() != 2 && cv.size() != 3) throw math_error(std::string(op) + ": 2 or 3 ciphertext elements expected");
+    const auto& ql = cv[0].GetParams()->Moduli();
+    for (const auto& c : cv) {
+        check_over(c, *cv[0].GetParams(), op, ": elements over one basis expected");
+        if (c.GetFormat() != cv[0].GetFormat() || c.Batch() != cv[0].Batch())
+            throw math_error(std::string(op) + ": elements of one format and one batch expected");
+    }
+    const auto& q = s.GetParams()->Moduli();
+    if (s.GetParams()->LogN() != cv[0].GetParams()->LogN() || q.size() < ql.size() ||
+        !std::equal(ql.begin(), ql.end(), q.begin()))
+        throw math_error(std::string(op) + ": the ciphertext's towers are not the first towers of the secret key's");
+    if (s.GetFormat() != Format::EVALUATION || s.Batch() != 1)
+        throw math_error(std::string(op) + ": the secret key in EVALUATION form, batch 1, expected");
+}
+
+// PKERNS::DecryptCore (rns-pke.cpp:199-224): b = c0 + c1 s (+ c2 s^2) over the
+// ciphertext's towers, COEFFICIENT-form elements transformed first.  The result
+// is in EVALUATION form, or with coeff_out in COEFFICIENT form, which is
+// PKECKKSRNS::Decrypt (ckksrns-pke.cpp:44-97) and PKERNS::Decrypt
+// (rns-pke.cpp:70-109) up to their last line: with one tower it is the
+// NativePoly, with more the caller's CRTInterpolate follows on the host.
+inline DCRTPolyHip DecryptCore(const std::vector<DCRTPolyHip>& cv, const DCRTPolyHip& s, bool coeff_out = false) {
+    check_ciphertext(cv, s, "DecryptCore");
+    const auto& Ql = cv[0].GetParams();
+    DCRTPolyHip b = DCRTPolyHip::result(Ql, coeff_out ? Format::COEFFICIENT : Format::EVALUATION, cv[0].Batch());
+    check(ofhe_hip_decrypt_core(Ql->plan(), (uint32_t)Ql->Towers(), (uint32_t)cv.size(),
+                                cv[0].GetFormat() == Format::EVALUATION, coeff_out, cv[0].data(), cv[1].data(),
+                                cv.size() == 3 ? cv[2].data() : nullptr, s.data(), b.data(), cv[0].Batch(), nullptr),
+          "DecryptCore");
+    return b;
+}
+
+// PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) over the chain Q for plaintext
+// modulus t; the library builds negtInvModq and qlInvModq from the moduli.
+//   ModReduceChain  the ModReduce steps Q_l -> q_0 (:55-60) of x over the first
+//                   towers of Q, COEFFICIENT -> the batch * N words on the host:
+//                   x_0 mod q_0, or with to_plaintext NativeVectorT::Mod(t) of it
+//   Decrypt         cv = 2 or 3 elements over the first towers of Q; EVALUATION
+//                   and COEFFICIENT elements take the reference's two branches
+//   ScalingFactor   the scalingFactorInt of FLEXIBLEAUTO / FLEXIBLEAUTOEXT
+//                   (:62-69, 82-89), host arithmetic on the caller's factors:
+//                   factors[l] is GetModReduceFactorInt(l)
+class BgvDecrypt {
+public:
+    BgvDecrypt(std::shared_ptr<DCRTParams> Q, uint64_t t) : Q_(std::move(Q)), t_(t) {
+        ofhe_bgv_decrypt_t h = nullptr;
+        check(ofhe_hip_bgv_decrypt_create(Q_->manager()->ctx(), Q_->LogN(), (uint32_t)Q_->Towers(),
+                                          Q_->Moduli().data(), t, &h),
+              "BgvDecrypt");
+        h_.reset(h);
+    }
+    std::vector<uint64_t> ModReduceChain(const DCRTPolyHip& x, bool to_plaintext) const {
+        check_form(x, Format::COEFFICIENT, "ModReduceChain");
+        const uint32_t size_ql = level_of(x, "ModReduceChain");
+        DeviceBuffer out(Q_->manager(), (size_t)x.Batch() * Q_->GetRingDimension());
+        check(ofhe_hip_bgv_mod_reduce_chain(h_.get(), size_ql, to_plaintext, x.data(), out.get(), x.Batch(), nullptr),
+              "ModReduceChain");
+        return fetch(out);
+    }
+    std::vector<uint64_t> Decrypt(const std::vector<DCRTPolyHip>& cv, const DCRTPolyHip& s) const {
+        check_ciphertext(cv, s, "Decrypt");
+        check_over(s, *Q_, "Decrypt", ": the secret key is over another basis");
+        const uint32_t size_ql = level_of(cv[0], "Decrypt");
+        DeviceBuffer out(Q_->manager(), (size_t)cv[0].Batch() * Q_->GetRingDimension());
+        check(ofhe_hip_bgv_decrypt(h_.get(), Q_->plan(), size_ql, (uint32_t)cv.size(),
+                                   cv[0].GetFormat() == Format::EVALUATION, cv[0].data(), cv[1].data(),
+                                   cv.size() == 3 ? cv[2].data() : nullptr, s.data(), out.get(), cv[0].Batch(),
+                                   nullptr),
+              "Decrypt");
+        return fetch(out);
+    }
+    static uint64_t ScalingFactor(uint64_t scalingFactorInt, const std::vector<uint64_t>& factors, size_t sizeQl,
+                                  uint64_t t) {
+        if (t < 2 || sizeQl < 1 || (sizeQl > 1 && factors.size() < sizeQl))
+            throw math_error("ScalingFactor: t >= 2 and one factor per level below sizeQl expected");
+        unsigned __int128 sf = scalingFactorInt % t;
+        for (size_t i = 0; i + 1 < sizeQl; i++) {
+            // NativeInteger::ModInverse(t) by the extended Euclidean algorithm
+            __int128 r0 = t, r1 = factors[sizeQl - 1 - i] % t, x0 = 0, x1 = 1;
+            while (r1) {
+                const __int128 qt = r0 / r1, r2 = r0 - qt * r1, x2 = x0 - qt * x1;
+                r0 = r1, r1 = r2, x0 = x1, x1 = x2;
+            }
+            if (r0 != 1) throw math_error("ScalingFactor: a factor is not invertible mod t");
+            sf = sf * (unsigned __int128)(x0 < 0 ? x0 + t : x0) % t;
+        }
+        return (uint64_t)sf;
+    }
+    const std::shared_ptr<DCRTParams>& GetParams() const { return Q_; }
+    uint64_t GetPlaintextModulus() const { return t_; }
+    ofhe_bgv_decrypt_t handle() const { return h_.get(); }
+
+private:
+    // x is over the first size_ql towers of Q
+    uint32_t level_of(const DCRTPolyHip& x, const char* op) const {
+        const auto &ql = x.GetParams()->Moduli(), &q = Q_->Moduli();
+        if (x.GetParams()->LogN() != Q_->LogN() || ql.size() > q.size() || !std::equal(ql.begin(), ql.end(), q.begin()))
+            throw math_error(std::string(op) + ": the polynomial is not over the first towers of the chain");
+        return (uint32_t)ql.size();
+    }
+    static std::vector<uint64_t> fetch(const DeviceBuffer& d) {
+        std::vector<uint64_t> h(d.size());
+        d.download(h.data());
+        return h;
+    }
+    std::shared_ptr<DCRTParams> Q_;
+    uint64_t t_;
+    Handle<ofhe_bgv_decrypt_s, ofhe_hip_bgv_decrypt_destroy> h_;
+};
+
+// BgvDecryptCache: one BgvDecrypt per (device, N, t, Q) -- the reference
+// precomputes negtInvModq / qlInvModq once per CryptoParametersBGVRNS
+// (bgvrns-cryptoparameters.cpp:91-107).
+class BgvDecryptCache {
+public:
+    static std::shared_ptr<BgvDecrypt> get(const std::shared_ptr<DCRTParams>& Q, uint64_t t) {
+        std::vector<uint64_t> key{(uint64_t)Q->manager()->device(), Q->LogN(), t};
+        key.insert(key.end(), Q->Moduli().begin(), Q->Moduli().end());
+        return Cache<std::vector<uint64_t>, BgvDecrypt>::get(key, [&] { return std::make_shared<BgvDecrypt>(Q, t); });
+    }
+};
 
 // ApproxModDown (dcrtpoly-impl.h:1134-1175): x over Q|P (EVALUATION) -> Q.
 inline DCRTPolyHip ApproxModDown(const DCRTPolyHip& x, const std::shared_ptr<DCRTParams>& paramsQ,

@@ -34,6 +34,12 @@ Host-side mirror of the reference's offload interface for the hot path:
   (rns-pke.cpp:199-224), the two ``ScaleAndRound`` overloads to a ``NativePoly`` mod t
   (dcrtpoly-impl.h:1537-1814, 2005-2049), the one-tower ``MultiplyAndRound`` path, and
   ``DCRTPolyImpl::TimesQovert`` (dcrtpoly-impl.h:1015-1031); its tables are a ``bfv_tables.DecryptTables``.
+* ``BgvDecrypt`` ~ ``PKEBGVRNS::Decrypt`` (bgvrns-pke.cpp:44-99): the ``DCRTPolyImpl::ModReduce`` chain
+  Q_l -> q_0 (dcrtpoly-impl.h:792-812) in one kernel per 8 towers, ``NativeVectorT::Mod(t)``
+  (mubintvecnat.cpp:139-166) and both of the reference's branches; its tables are built by the library from the
+  moduli.  ``NTTPlan.decrypt_core`` ~ ``PKERNS::DecryptCore`` (rns-pke.cpp:199-224), which with ``coeff_out`` is
+  ``PKECKKSRNS::Decrypt`` / ``PKERNS::Decrypt`` up to their last line; ``bgv_scaling_factor`` is the host
+  arithmetic on ``scalingFactorInt`` (bgvrns-pke.cpp:62-69).
 * ``KeySwitch.eval_mult`` / ``eval_square`` / ``relinearize`` / ``rescale`` ~ ``LeveledSHEBase::EvalMult`` /
   ``EvalSquare`` with an evaluation key and ``RelinearizeInPlace`` (base-leveledshe.cpp:199-372) and
   ``ModReduceInternalInPlace`` of CKKS and BGV (ckksrns-leveledshe.cpp:107-132, bgvrns-leveledshe.cpp:45-77).
@@ -232,6 +238,15 @@ _SIGS = {
     "ofhe_hip_bfv_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
                                             ctypes.c_uint32, _vp]),
     "ofhe_hip_times_q_over_t": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_bgv_decrypt_create": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_uint64,
+                                                   ctypes.POINTER(_vp)]),
+    "ofhe_hip_bgv_decrypt_destroy": (ctypes.c_int, [_vp]),
+    "ofhe_hip_bgv_mod_reduce_chain": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32,
+                                                     _vp]),
+    "ofhe_hip_bgv_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp,
+                                            _vp, _vp, ctypes.c_uint32, _vp]),
+    "ofhe_hip_decrypt_core": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp,
+                                             _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "ofhe_hip_comm_unique_id": (ctypes.c_int, [_vp]),
     "ofhe_hip_comm_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "ofhe_hip_comm_destroy": (ctypes.c_int, [_vp]),
@@ -240,6 +255,8 @@ _SIGS = {
 
 COMM_ID_BYTES = 128  # OFHE_COMM_ID_BYTES
 BEHZ_FUSED_MAX_B = 16  # OFHE_BEHZ_FUSED_MAX_B: most B towers of the fused floor -> SK launch
+BGV_DECRYPT_MAX_TOWERS = 64  # OFHE_BGV_DECRYPT_MAX_TOWERS: most towers of a BgvDecrypt handle
+BGV_CHAIN_K = 8  # towers one launch of the ModReduce chain retires (csrc/bgv_decrypt_kernels.hpp); more run in passes
 KS_ROT_CAP = 16  # rotations per launch of the hoisted-rotation calls (csrc/ks_kernels.hpp); more run in chunks
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -275,6 +292,13 @@ def _arr(vals: Sequence[int]):
 def _ptrs(v):
     """Host array of device pointers; None stays NULL, a 0 entry a NULL entry."""
     return None if v is None else (_vp * len(v))(*[int(p) or None for p in v])
+
+
+def _c012(elements: Sequence[int]):
+    """The C ABI's (c0, c1, c2) of a ciphertext of 2 or 3 device pointers: a missing c2 is NULL; the count is
+    checked by the library."""
+    c = [int(p) for p in elements] + [0] * (3 - len(elements))
+    return [_vp(p or None) for p in c[:3]]
 
 
 def version() -> str:
@@ -574,6 +598,16 @@ class NTTPlan(_Handle):
         _check(lib().ofhe_hip_bv_key_switch(self.handle, int(towers), int(digit_size), _vp(c), _vp(key_b), _vp(key_a),
                                             int(key_towers), _vp(add0 or None), _vp(add1 or None), _vp(out0),
                                             _vp(out1), int(chunk_digits), int(batch), _vp(stream or None)))
+
+    # --- PKERNS::DecryptCore (rns-pke.cpp:199-224) ---
+    def decrypt_core(self, size_ql: int, elements: Sequence[int], s: int, out: int, eval_form: bool = True,
+                     coeff_out: bool = False, batch: int = 1, stream: int = 0) -> None:
+        """out = c0 + c1 s (+ c2 s^2) over the first size_ql towers; elements: the 2 or 3 device pointers, each
+        [batch][size_ql][N]; coeff_out adds the INTT (PKECKKSRNS::Decrypt / PKERNS::Decrypt up to their last
+        line).  out may be elements[0]."""
+        _check(lib().ofhe_hip_decrypt_core(self.handle, int(size_ql), len(elements), 1 if eval_form else 0,
+                                           1 if coeff_out else 0, *_c012(elements), _vp(s), _vp(out), int(batch),
+                                           _vp(stream or None)))
 
     # --- LeveledSHEBase::EvalMultCore, 2 x 2 elements (base-leveledshe.cpp:667-672) ---
     def eval_mult_core(self, c0: int, c1: int, d0: int, d1: int, out0: int, out1: int, out2: int, batch: int = 1,
@@ -878,13 +912,61 @@ class BfvDecrypt(_Handle):
     def decrypt(self, plan_q: NTTPlan, elements: Sequence[int], s: int, out: int, eval_form: bool, batch: int = 1,
                 stream: int = 0) -> None:
         """elements: the 2 or 3 device pointers c0, c1 (, c2)."""
-        c = [int(p) for p in elements] + [0] * (3 - len(elements))
-        _check(lib().ofhe_hip_bfv_decrypt(self._h, plan_q.handle, len(elements), 1 if eval_form else 0, _vp(c[0]),
-                                          _vp(c[1]), _vp(c[2] or None), _vp(s), _vp(out), int(batch),
-                                          _vp(stream or None)))
+        _check(lib().ofhe_hip_bfv_decrypt(self._h, plan_q.handle, len(elements), 1 if eval_form else 0,
+                                          *_c012(elements), _vp(s), _vp(out), int(batch), _vp(stream or None)))
 
     def times_q_over_t(self, x: int, out: int, batch: int = 1, stream: int = 0) -> None:
         _check(lib().ofhe_hip_times_q_over_t(self._h, _vp(x), _vp(out), int(batch), _vp(stream or None)))
+
+
+class BgvDecrypt(_Handle):
+    """PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) for ciphertext towers `moduli` and plaintext modulus t; the
+    library builds negtInvModq and qlInvModq (bgvrns-cryptoparameters.cpp:91-107) from them.
+
+    * ``mod_reduce_chain``  the ModReduce steps Q_l -> q_0 of a coefficient-form x [batch][size_ql][N] ->
+      out [batch][N]: x_0 mod q_0, or with ``to_plaintext`` NativeVectorT::Mod(t) of it.
+    * ``decrypt``           2 or 3 elements [batch][size_ql][N] and the secret key [size_q][N] (evaluation form)
+      -> out [batch][N]; evaluation-form and coefficient-form elements take the reference's two branches."""
+
+    _destroy = "ofhe_hip_bgv_decrypt_destroy"
+
+    def __init__(self, ctx: Context, log_n: int, moduli: Sequence[int], t: int):
+        self.ctx, self.log_n, self.t = ctx, int(log_n), int(t)
+        self.moduli = [int(q) for q in moduli]
+        self.size_q = len(self.moduli)
+        h = _vp()
+        _check(lib().ofhe_hip_bgv_decrypt_create(ctx.handle if ctx is not None else None, self.log_n, self.size_q,
+                                                 _arr(self.moduli), self.t, ctypes.byref(h)))
+        self._h = h
+
+    def mod_reduce_chain(self, size_ql: int, x: int, out: int, to_plaintext: bool, batch: int = 1,
+                         stream: int = 0) -> None:
+        _check(lib().ofhe_hip_bgv_mod_reduce_chain(self._h, int(size_ql), 1 if to_plaintext else 0, _vp(x), _vp(out),
+                                                   int(batch), _vp(stream or None)))
+
+    def decrypt(self, plan_q: NTTPlan, size_ql: int, elements: Sequence[int], s: int, out: int, eval_form: bool,
+                batch: int = 1, stream: int = 0) -> None:
+        """elements: the 2 or 3 device pointers c0, c1 (, c2)."""
+        _check(lib().ofhe_hip_bgv_decrypt(self._h, plan_q.handle, int(size_ql), len(elements), 1 if eval_form else 0,
+                                          *_c012(elements), _vp(s), _vp(out), int(batch), _vp(stream or None)))
+
+
+def bgv_scaling_factor(scaling_factor_int: int, mod_reduce_factors: Sequence[int], size_ql: int, t: int) -> int:
+    """The scalingFactorInt PKEBGVRNS::Decrypt returns under FLEXIBLEAUTO / FLEXIBLEAUTOEXT (bgvrns-pke.cpp:62-69,
+    82-89; the same in both branches), on the host: the ciphertext's factor times the inverse mod t of
+    mod_reduce_factors[size_ql - 1 - i] for i < size_ql - 1, where mod_reduce_factors[l] is the caller's
+    GetModReduceFactorInt(l).  Under the FIXED techniques the reference returns the factor unchanged."""
+    t, sf, size_ql = int(t), int(scaling_factor_int), int(size_ql)
+    if t < 2 or size_ql < 1 or (size_ql > 1 and len(mod_reduce_factors) < size_ql):
+        raise MathError("bgv_scaling_factor: t >= 2 and one factor per level below size_ql expected")
+    for i in range(size_ql - 1):
+        f = int(mod_reduce_factors[size_ql - 1 - i]) % t
+        try:
+            inv = pow(f, -1, t)
+        except ValueError:
+            raise MathError(f"bgv_scaling_factor: factor {size_ql - 1 - i} is not invertible mod t") from None
+        sf = sf % t * inv % t
+    return sf
 
 
 def approx_mod_down(plan_q: NTTPlan, plan_p: NTTPlan, p_to_q: BaseConverter, p_inv_modq: Sequence[int], t: int,
