@@ -232,261 +232,10 @@ __device__ __forceinline__ void triv_bfly(u64& x, u64& y, u64 bq) {
 }
 
 // DIT stage of a radix-16 register round with element stride st: the thread
-// holds v[k] = x[p0 + k st], r = p0 mod st; half = 2^H pairs (k, k + half),
-// twiddle index st half + r + st (k mod half) -- base points at entry
-// st half + r.  CS: conditional-subtract stage (inputs < 16q, else < 12q).
-template <int H, int CS, class M_>
-__device__ __forceinline__ void dit_stage16(u64 (&v)[16], const u64* base, u32 st, const M_& M) {
-    constexpr int half = 1 << H;
-#pragma unroll
-    for (int j = 0; j < half; j++) {
-        const Tw w = ldtw(base, st * j);
-#pragma unroll
-        for (int g = 0; g < 16; g += 2 * half) ct_bfly<CS>(v[g + j], v[g + j + half], w, M);
-    }
-}
-template <class M_>
-__device__ __forceinline__ void dit_round16(u64 (&v)[16], const u64* dtw, u32 st, u32 r, const M_& M) {
-    dit_stage16<0, 1>(v, dtw + 2 * ((u64)st + r), st, M);
-    dit_stage16<1, 0>(v, dtw + 2 * ((u64)2 * st + r), st, M);
-    dit_stage16<2, 1>(v, dtw + 2 * ((u64)4 * st + r), st, M);
-    dit_stage16<3, 0>(v, dtw + 2 * ((u64)8 * st + r), st, M);
-}
-
-// The first four DIT stages (t = 1, 2, 4, 8) on 16 consecutive elements, inputs
-// < 2q (the Montgomery Hadamard's (0, 2q) or canonical data): twiddles
-// dtw[t + j] are the same for every thread, j = 0 is w = 1.
-//   t = 1: all trivial, -> < 4q;  t = 2: -> < 8q;  t = 4: -> < 16q (trivial)
-//   / < 12q;  t = 8: conditional subtract first, -> < 16q.
-template <bool SPQ, bool QA>
-__device__ __forceinline__ void dit_round3(u64 (&v)[16], const u64* dtw, const Mod<SPQ, QA>& M) {
-#pragma unroll
-    for (int g = 0; g < 16; g += 2) triv_bfly(v[g], v[g + 1], 2 * M.q);
-#pragma unroll
-    for (int g = 0; g < 16; g += 4) triv_bfly(v[g], v[g + 2], M.q4);
-    {
-        const Tw w = ldtw(dtw, 3);
-#pragma unroll
-        for (int g = 0; g < 16; g += 4) ct_bfly<0>(v[g + 1], v[g + 3], w, M);
-    }
-#pragma unroll
-    for (int g = 0; g < 16; g += 8) triv_bfly(v[g], v[g + 4], M.q8);
-#pragma unroll
-    for (int j = 1; j < 4; j++) {
-        const Tw w = ldtw(dtw, 4 + j);
-#pragma unroll
-        for (int g = 0; g < 16; g += 8) ct_bfly<0>(v[g + j], v[g + j + 4], w, M);
-    }
-    {
-        const u64 a = red16(v[0], M), b = red16(v[8], M);
-        v[0] = a;
-        v[8] = b;
-        triv_bfly(v[0], v[8], M.q8);
-    }
-#pragma unroll
-    for (int j = 1; j < 8; j++) ct_bfly<1>(v[j], v[j + 8], ldtw(dtw, 8 + j), M);
-}
-
-// last step of every inverse: x * N^-1 psi^-j (the twist entry f) -> [0, q)
-template <bool SPQ, bool QA>
-__device__ __forceinline__ u64 twist_out(u64 x, Tw f, const Mod<SPQ, QA>& M) {
-    return canon4m(shoup_lazy(x, f.w, f.wp, M), M);
-}
-
-// ---------------------------------------------------------------------------
-// Register radix-16 rounds.  A thread holds v[k] = x[p0 + k*st], k < 16, where
-// p0 = hb*16*st + r (r < st).  Stage s (s = 0..3, t = st * 2^(3-s)) pairs
-// (k, k + 2^(3-s)); its twiddle index is 2^s * M0 + (k >> (4 - s)) with
-// M0 = N/(16 st) + (global index of the 16*st super-group).
-// ---------------------------------------------------------------------------
-template <int S, class M_, int CS = S & 1>
-__device__ __forceinline__ void fwd_stage16(u64 (&v)[16], const u64* tw, u32 M0, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = tw + 2 * ((u64)M0 << S);  // one address per stage, j as immediate offsets
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base, j);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++) ct_bfly<CS>(v[k], v[k + half], w, M);
-    }
-}
-
-template <int S, class M_>
-__device__ __forceinline__ void inv_stage16(u64 (&v)[16], const u64* itw, u32 M0, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = itw + 2 * ((u64)M0 << S);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base, j);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++) gs_bfly(v[k], v[k + half], w, M);
-    }
-}
-
-// Lazy GS radix-16 round for the inverse column pass.  The
-// bound of every register is known at compile time (b8[k]: < 8q, else < 4q):
-// a GS butterfly's sum output is < 8q and its Shoup output < 4q whatever the
-// inputs, so only butterflies with an 8q input take the conditional subtract
-// (12 of 32 in a round fed with < 4q, 20 of 32 fed with < 8q) and the rest
-// add straight through.  d = x + Bq - y < 16q <= 2^64 (q < 2^60).
-template <class M_>
-__device__ __forceinline__ void gs_bfly_b(u64& x, u64& y, Tw w, const M_& M, bool in8) {
-    const u64 s = x + y;
-    const u64 d = x + (in8 ? M.q8 : M.q4) - y;
-    x = in8 ? red16_gs(s, M) : s;
-    y = shoup_lazy(d, w.w, w.wp, M);
-}
-template <int S, class M_>
-__device__ __forceinline__ void inv_stage16_b(u64 (&v)[16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = itw + 2 * ((u64)M0 << S);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base, j);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++) {
-            gs_bfly_b(v[k], v[k + half], w, M, b8[k] || b8[k + half]);
-            b8[k] = true;
-            b8[k + half] = false;
-        }
-    }
-}
-template <class M_>
-__device__ __forceinline__ void inv_round16_b(u64 (&v)[16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
-    inv_stage16_b<3>(v, b8, itw, M0, M);
-    inv_stage16_b<2>(v, b8, itw, M0, M);
-    inv_stage16_b<1>(v, b8, itw, M0, M);
-    inv_stage16_b<0>(v, b8, itw, M0, M);
-}
-
-template <class M_>
-__device__ __forceinline__ void fwd_round16(u64 (&v)[16], const u64* tw, u32 M0, const M_& M) {
-    fwd_stage16<0>(v, tw, M0, M);
-    fwd_stage16<1>(v, tw, M0, M);
-    fwd_stage16<2>(v, tw, M0, M);
-    fwd_stage16<3>(v, tw, M0, M);
-}
-// First round of a forward transform on canonical input:
-// [0, q) -> 5q -> 9q -> 13q without a conditional subtract, then the CS stage
-// -> [0, 12q), the bound the alternating schedule leaves after any round.
-// Needs inputs < 4q (canonical, per the C ABI contract).
-template <class M_>
-__device__ __forceinline__ void fwd_round16_canon(u64 (&v)[16], const u64* tw, u32 M0, const M_& M) {
-    fwd_stage16<0>(v, tw, M0, M);
-    fwd_stage16<1, M_, 0>(v, tw, M0, M);
-    fwd_stage16<2>(v, tw, M0, M);
-    fwd_stage16<3>(v, tw, M0, M);
-}
-template <class M_>
-__device__ __forceinline__ void inv_round16(u64 (&v)[16], const u64* itw, u32 M0, const M_& M) {
-    inv_stage16<3>(v, itw, M0, M);
-    inv_stage16<2>(v, itw, M0, M);
-    inv_stage16<1>(v, itw, M0, M);
-    inv_stage16<0>(v, itw, M0, M);
-}
-
-// ---------------------------------------------------------------------------
-// Round 3 of k_block (st = 1) gives every thread its own twiddles: thread u
-// of the block's 256 (global u = 256 g + tid, M0 = N/16 + u) needs
-// Table[(M0 << S) + j], j < 2^S.  Read from Table directly, lanes are 2^S
-// entries apart and one wave-wide 16-byte load touches 64 cache lines.  The
-// plan therefore also stores these twiddles transposed, tw3[S][j][u] at
-// ((2^S - 1) U + j U + u) with U = N/16, so a wave reads 1 KiB contiguous per
-// load, from a uniform (scalar) base plus the lane offset.
-//
-// The fused pipeline's Hadamard is a Montgomery product on the lazy forward
-// output (< 12q after round 3's CS stage, which mont_mul accepts; no
-// canonicalisation, no Barrett), and the 2^-64 it introduces is cancelled by
-// 2^64 folded into the inverse's N^-1 twist (PlanArgs::twist = the plan's
-// twist_r table).  Intermediate values differ in representation only; the
-// canonical output is the same integer.
-//
-// k_block's round-3 layout gives each thread 16 consecutive words, so direct
-// global access would be one 128-byte line per lane per instruction.  The
-// inverse input, the forward output and the second operand go through the
-// wave's own LDS slots instead (wave_stage_*).
-// ---------------------------------------------------------------------------
-template <int S, class M_>
-__device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[16], const u64* tw3, u32 U, u32 u, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = tw3 + 2 * (u64)(((1u << S) - 1) * U);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base + 2 * (u64)j * U, u);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++) ct_bfly<S & 1>(v[k], v[k + half], w, M);
-    }
-}
-// ---------------------------------------------------------------------------
-// The same stages on Q register sets per thread (block_body_q2's two
-// polynomial quads): every twiddle or twist entry is fetched once and applied
-// to all sets before the next fetch, as cols_fwd's columns.  Per set, the
-// operations and their order are those of the one-set helpers above.
-// ---------------------------------------------------------------------------
-template <int S, int Q, class M_, int CS = S & 1>
-__device__ __forceinline__ void fwd_stage16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = tw + 2 * ((u64)M0 << S);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base, j);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
-#pragma unroll
-            for (int c = 0; c < Q; c++) ct_bfly<CS>(v[c][k], v[c][k + half], w, M);
-    }
-}
-template <int Q, class M_>
-__device__ __forceinline__ void fwd_round16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
-    fwd_stage16<0>(v, tw, M0, M);
-    fwd_stage16<1>(v, tw, M0, M);
-    fwd_stage16<2>(v, tw, M0, M);
-    fwd_stage16<3>(v, tw, M0, M);
-}
-template <int Q, class M_>
-__device__ __forceinline__ void fwd_round16_canon(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
-    fwd_stage16<0>(v, tw, M0, M);
-    fwd_stage16<1, Q, M_, 0>(v, tw, M0, M);
-    fwd_stage16<2>(v, tw, M0, M);
-    fwd_stage16<3>(v, tw, M0, M);
-}
-// one b8[16] for all sets: a register's bound depends on its position only
-template <int S, int Q, class M_>
-__device__ __forceinline__ void inv_stage16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = itw + 2 * ((u64)M0 << S);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base, j);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++) {
-#pragma unroll
-            for (int c = 0; c < Q; c++) gs_bfly_b(v[c][k], v[c][k + half], w, M, b8[k] || b8[k + half]);
-            b8[k] = true;
-            b8[k + half] = false;
-        }
-    }
-}
-template <int Q, class M_>
-__device__ __forceinline__ void inv_round16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
-    inv_stage16_b<3>(v, b8, itw, M0, M);
-    inv_stage16_b<2>(v, b8, itw, M0, M);
-    inv_stage16_b<1>(v, b8, itw, M0, M);
-    inv_stage16_b<0>(v, b8, itw, M0, M);
-}
-template <int S, int Q, class M_>
-__device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[Q][16], const u64* tw3, u32 U, u32 u, const M_& M) {
-    constexpr int half = 8 >> S;
-    const u64* base = tw3 + 2 * (u64)(((1u << S) - 1) * U);
-#pragma unroll
-    for (int j = 0; j < (1 << S); j++) {
-        Tw w = ldtw(base + 2 * (u64)j * U, u);
-#pragma unroll
-        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
-#pragma unroll
-            for (int c = 0; c < Q; c++) ct_bfly<S & 1>(v[c][k], v[c][k + half], w, M);
-    }
-}
+// holds v[c][k] = x_c[p0 + k st] of Q register sets (see below), r = p0 mod st;
+// half = 2^H pairs (k, k + half), twiddle index st half + r + st (k mod half)
+// -- base points at entry st half + r.  CS: conditional-subtract stage
+// (inputs < 16q, else < 12q).
 template <int H, int CS, int Q, class M_>
 __device__ __forceinline__ void dit_stage16(u64 (&v)[Q][16], const u64* base, u32 st, const M_& M) {
     constexpr int half = 1 << H;
@@ -506,6 +255,12 @@ __device__ __forceinline__ void dit_round16(u64 (&v)[Q][16], const u64* dtw, u32
     dit_stage16<2, 1>(v, dtw + 2 * ((u64)4 * st + r), st, M);
     dit_stage16<3, 0>(v, dtw + 2 * ((u64)8 * st + r), st, M);
 }
+
+// The first four DIT stages (t = 1, 2, 4, 8) on 16 consecutive elements, inputs
+// < 2q (the Montgomery Hadamard's (0, 2q) or canonical data): twiddles
+// dtw[t + j] are the same for every thread, j = 0 is w = 1.
+//   t = 1: all trivial, -> < 4q;  t = 2: -> < 8q;  t = 4: -> < 16q (trivial)
+//   / < 12q;  t = 8: conditional subtract first, -> < 16q.
 template <int Q, bool SPQ, bool QA>
 __device__ __forceinline__ void dit_round3(u64 (&v)[Q][16], const u64* dtw, const Mod<SPQ, QA>& M) {
 #pragma unroll
@@ -546,6 +301,152 @@ __device__ __forceinline__ void dit_round3(u64 (&v)[Q][16], const u64* dtw, cons
         const Tw w = ldtw(dtw, 8 + j);
 #pragma unroll
         for (int c = 0; c < Q; c++) ct_bfly<1>(v[c][j], v[c][j + 8], w, M);
+    }
+}
+
+// last step of every inverse: x * N^-1 psi^-j (the twist entry f) -> [0, q)
+template <bool SPQ, bool QA>
+__device__ __forceinline__ u64 twist_out(u64 x, Tw f, const Mod<SPQ, QA>& M) {
+    return canon4m(shoup_lazy(x, f.w, f.wp, M), M);
+}
+
+// ---------------------------------------------------------------------------
+// Register radix-16 rounds.  A thread holds v[k] = x[p0 + k*st], k < 16, where
+// p0 = hb*16*st + r (r < st).  Stage s (s = 0..3, t = st * 2^(3-s)) pairs
+// (k, k + 2^(3-s)); its twiddle index is 2^s * M0 + (k >> (4 - s)) with
+// M0 = N/(16 st) + (global index of the 16*st super-group).
+//
+// Every round helper here and above (dit_*) takes Q such register sets per
+// thread, v[c][k], c < Q, that share their twiddles: the two polynomial quads
+// of block_body_q2, the two columns of tcols_pairs_*, and Q = 1 for the
+// one-set bodies, which declare v1[1][16].  A twiddle is fetched once and
+// applied to all sets before the next fetch, as cols_fwd's columns; per set the
+// operations and their order do not depend on Q.  These helpers carry the
+// lazy-reduction schedule (which stage takes the conditional subtract, the b8
+// bounds), so each of them exists once.
+// ---------------------------------------------------------------------------
+template <int S, int Q, class M_, int CS = S & 1>
+__device__ __forceinline__ void fwd_stage16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = tw + 2 * ((u64)M0 << S);  // one address per stage, j as immediate offsets
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base, j);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<CS>(v[c][k], v[c][k + half], w, M);
+    }
+}
+
+template <int S, class M_>
+__device__ __forceinline__ void inv_stage16(u64 (&v)[16], const u64* itw, u32 M0, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = itw + 2 * ((u64)M0 << S);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base, j);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++) gs_bfly(v[k], v[k + half], w, M);
+    }
+}
+
+// Lazy GS radix-16 round for the inverse column pass.  The
+// bound of every register is known at compile time (b8[k]: < 8q, else < 4q):
+// a GS butterfly's sum output is < 8q and its Shoup output < 4q whatever the
+// inputs, so only butterflies with an 8q input take the conditional subtract
+// (12 of 32 in a round fed with < 4q, 20 of 32 fed with < 8q) and the rest
+// add straight through.  d = x + Bq - y < 16q <= 2^64 (q < 2^60).
+template <class M_>
+__device__ __forceinline__ void gs_bfly_b(u64& x, u64& y, Tw w, const M_& M, bool in8) {
+    const u64 s = x + y;
+    const u64 d = x + (in8 ? M.q8 : M.q4) - y;
+    x = in8 ? red16_gs(s, M) : s;
+    y = shoup_lazy(d, w.w, w.wp, M);
+}
+// one b8[16] for all sets: a register's bound depends on its position only
+template <int S, int Q, class M_>
+__device__ __forceinline__ void inv_stage16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = itw + 2 * ((u64)M0 << S);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base, j);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++) {
+#pragma unroll
+            for (int c = 0; c < Q; c++) gs_bfly_b(v[c][k], v[c][k + half], w, M, b8[k] || b8[k + half]);
+            b8[k] = true;
+            b8[k + half] = false;
+        }
+    }
+}
+template <int Q, class M_>
+__device__ __forceinline__ void inv_round16_b(u64 (&v)[Q][16], bool (&b8)[16], const u64* itw, u32 M0, const M_& M) {
+    inv_stage16_b<3>(v, b8, itw, M0, M);
+    inv_stage16_b<2>(v, b8, itw, M0, M);
+    inv_stage16_b<1>(v, b8, itw, M0, M);
+    inv_stage16_b<0>(v, b8, itw, M0, M);
+}
+
+template <int Q, class M_>
+__device__ __forceinline__ void fwd_round16(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    fwd_stage16<0>(v, tw, M0, M);
+    fwd_stage16<1>(v, tw, M0, M);
+    fwd_stage16<2>(v, tw, M0, M);
+    fwd_stage16<3>(v, tw, M0, M);
+}
+// First round of a forward transform on canonical input:
+// [0, q) -> 5q -> 9q -> 13q without a conditional subtract, then the CS stage
+// -> [0, 12q), the bound the alternating schedule leaves after any round.
+// Needs inputs < 4q (canonical, per the C ABI contract).
+template <int Q, class M_>
+__device__ __forceinline__ void fwd_round16_canon(u64 (&v)[Q][16], const u64* tw, u32 M0, const M_& M) {
+    fwd_stage16<0>(v, tw, M0, M);
+    fwd_stage16<1, Q, M_, 0>(v, tw, M0, M);
+    fwd_stage16<2>(v, tw, M0, M);
+    fwd_stage16<3>(v, tw, M0, M);
+}
+template <class M_>
+__device__ __forceinline__ void inv_round16(u64 (&v)[16], const u64* itw, u32 M0, const M_& M) {
+    inv_stage16<3>(v, itw, M0, M);
+    inv_stage16<2>(v, itw, M0, M);
+    inv_stage16<1>(v, itw, M0, M);
+    inv_stage16<0>(v, itw, M0, M);
+}
+
+// ---------------------------------------------------------------------------
+// Round 3 of k_block (st = 1) gives every thread its own twiddles: thread u
+// of the block's 256 (global u = 256 g + tid, M0 = N/16 + u) needs
+// Table[(M0 << S) + j], j < 2^S.  Read from Table directly, lanes are 2^S
+// entries apart and one wave-wide 16-byte load touches 64 cache lines.  The
+// plan therefore also stores these twiddles transposed, tw3[S][j][u] at
+// ((2^S - 1) U + j U + u) with U = N/16, so a wave reads 1 KiB contiguous per
+// load, from a uniform (scalar) base plus the lane offset.
+//
+// The fused pipeline's Hadamard is a Montgomery product on the lazy forward
+// output (< 12q after round 3's CS stage, which mont_mul accepts; no
+// canonicalisation, no Barrett), and the 2^-64 it introduces is cancelled by
+// 2^64 folded into the inverse's N^-1 twist (PlanArgs::twist = the plan's
+// twist_r table).  Intermediate values differ in representation only; the
+// canonical output is the same integer.
+//
+// k_block's round-3 layout gives each thread 16 consecutive words, so direct
+// global access would be one 128-byte line per lane per instruction.  The
+// inverse input, the forward output and the second operand go through the
+// wave's own LDS slots instead (wave_stage_*).
+// ---------------------------------------------------------------------------
+template <int S, int Q, class M_>
+__device__ __forceinline__ void fwd_stage16_t3(u64 (&v)[Q][16], const u64* tw3, u32 U, u32 u, const M_& M) {
+    constexpr int half = 8 >> S;
+    const u64* base = tw3 + 2 * (u64)(((1u << S) - 1) * U);
+#pragma unroll
+    for (int j = 0; j < (1 << S); j++) {
+        Tw w = ldtw(base + 2 * (u64)j * U, u);
+#pragma unroll
+        for (int k = j * 2 * half; k < j * 2 * half + half; k++)
+#pragma unroll
+            for (int c = 0; c < Q; c++) ct_bfly<S & 1>(v[c][k], v[c][k + half], w, M);
     }
 }
 
@@ -714,7 +615,8 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
     const u32 L1 = tid + h;      // lds_pad(tid + 256 k)      = L1 + 272 k
     const u32 L2 = h * 272 + r;  // lds_pad(256 h + r + 16 k) = L2 + 17 k
     const u32 L3 = tid * 17;     // lds_pad(16 tid + k)       = L3 + k
-    u64 v[16];
+    u64 v1[1][16];  // one register set: the round helpers' Q = 1
+    u64(&v)[16] = v1[0];
 
     if (MODE == MODE_FWD || MODE == MODE_FUSED || MODE == MODE_FWD_SUB || MODE == MODE_FWD_SUB_ADD) {
         if (NR == 3) {
@@ -722,9 +624,9 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = ld_s(blk + tid + 256 * k);
             if (SK == 3)
-                fwd_stage16<3>(v, tw, (N >> 12) + g, M);  // input < 12q (k_tcols) -> < 12q
+                fwd_stage16<3>(v1, tw, (N >> 12) + g, M);  // input < 12q (k_tcols) -> < 12q
             else
-                fwd_round16(v, tw, (N >> 12) + g, M);
+                fwd_round16(v1, tw, (N >> 12) + g, M);
 #pragma unroll
             for (int k = 0; k < 16; k++) lds[L1 + 272 * k] = v[k];
             __syncthreads();
@@ -736,7 +638,7 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
             for (int k = 0; k < 16; k++) v[k] = ld_s(blk + r + 16 * k);
         }
         // NR = 2: g is the group and wave-uniform, so these are scalar loads
-        fwd_round16(v, tw, (N >> 8) + (TEAM ? g : g * 16 + h), M);
+        fwd_round16(v1, tw, (N >> 8) + (TEAM ? g : g * 16 + h), M);
 #pragma unroll
         for (int k = 0; k < 16; k++) lds[L2 + 17 * k] = v[k];
         block_sync<NR>();
@@ -754,10 +656,10 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
         {
             const u64* tw3 = P.tw3 + (u64)t * (N / 16) * 30;
             const u32 U = N >> 4, u = TEAM ? g * 16 + r : g * 256 + tid;
-            fwd_stage16_t3<0>(v, tw3, U, u, M);
-            fwd_stage16_t3<1>(v, tw3, U, u, M);
-            fwd_stage16_t3<2>(v, tw3, U, u, M);
-            fwd_stage16_t3<3>(v, tw3, U, u, M);
+            fwd_stage16_t3<0>(v1, tw3, U, u, M);
+            fwd_stage16_t3<1>(v1, tw3, U, u, M);
+            fwd_stage16_t3<2>(v1, tw3, U, u, M);
+            fwd_stage16_t3<3>(v1, tw3, U, u, M);
         }
         if (MODE == MODE_FWD) {
 #pragma unroll
@@ -804,13 +706,13 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
     // position / G): canonical when the block ran every stage (N = 2^12),
     // else lazy [0, 4q) for the GS column pass
     const u64* dtw = P.dtw + (u64)t * N * 2;
-    dit_round3(v, dtw, M);
+    dit_round3(v1, dtw, M);
 #pragma unroll
     for (int k = 0; k < 16; k++) lds[L3 + k] = v[k];
     block_sync<NR>();
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = lds[L2 + 17 * k];
-    dit_round16(v, dtw, 16, r, M);
+    dit_round16(v1, dtw, 16, r, M);
     const u64* tw_ = P.twist + (u64)t * N * 2 + 2 * ((u64)g << (TEAM ? 8 : 12));
     if (NR == 2) {
         // twist into the GS column pass's input, lazy [0, 4q); the same
@@ -832,9 +734,9 @@ __device__ __forceinline__ void block_body(const PlanArgs& P, const u64* src, u6
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = lds[L1 + 272 * k];
     if (SK == 3)
-        dit_stage16<0, 1>(v, dtw + 2 * ((u64)256 + tid), 256, M);  // t = 256 only: < 16q -> < 12q
+        dit_stage16<0, 1>(v1, dtw + 2 * ((u64)256 + tid), 256, M);  // t = 256 only: < 16q -> < 12q
     else
-        dit_round16(v, dtw, 256, tid, M);
+        dit_round16(v1, dtw, 256, tid, M);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         const Tw f = ldtw(tw_, tid + 256 * k);
@@ -1255,7 +1157,8 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
     const Mod<SPQ> M = load_mod<SPQ>(tc);
     const u32 h = tid / W, r = tid % W;
     const u32 L1 = tid, L2 = h * 16 * W + r;
-    u64 v[16];
+    u64 v1[1][16];  // one register set: the round helpers' Q = 1
+    u64(&v)[16] = v1[0];
     if (!INV) {
         const u64* tw = P.tw + (u64)t * N * 2;
         constexpr u32 RP = 16 * W + 16;  // padded row pitch
@@ -1275,14 +1178,14 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = ld_s(x + (u64)(h + 16 * k) * S + r);
         }
-        fwd_round16_canon(v, tw, 1, M);
+        fwd_round16_canon(v1, tw, 1, M);
 #pragma unroll
         for (int k = 0; k < 16; k++) lds[L1 + RP * k] = v[k];
         __syncthreads();
         // round 2: rows 16h + k (p = 16W h + W k + r), stages m = 16..128
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = lds[h * RP + r + W * k];
-        fwd_round16(v, tw, 16 + h, M);
+        fwd_round16(v1, tw, 16 + h, M);
 #pragma unroll
         for (int k = 0; k < 16; k++) st_s(y + (u64)(16 * h + k) * S + r, v[k]);
     } else {
@@ -1294,7 +1197,7 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
         bool b8[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) b8[k] = false;
-        inv_round16_b(v, b8, itw, 16 + h, M);
+        inv_round16_b(v1, b8, itw, 16 + h, M);
 #pragma unroll
         for (int k = 0; k < 16; k++) lds[L2 + W * k] = v[k];
         __syncthreads();
@@ -1303,7 +1206,7 @@ __device__ __forceinline__ void tcols_body(const PlanArgs& P, const u64* src, u6
             v[k] = lds[L1 + 16 * W * k];
             b8[k] = true;
         }
-        inv_round16_b(v, b8, itw, 1, M);
+        inv_round16_b(v1, b8, itw, 1, M);
 #pragma unroll
         for (int k = 0; k < 16; k++)
             st_s(y + (u64)(h + 16 * k) * S + r, b8[k] ? canon8m(v[k], M) : canon4m(v[k], M));
@@ -1353,7 +1256,8 @@ __global__ __launch_bounds__(512) void k_tcols9(PlanArgs P, const u64* src, u64*
     u64* my = lds + hf * HALF;
     const u64* other = lds + (hf ^ 1) * HALF;
     const u32 L1 = tl, L2 = h * 16 * W + r;
-    u64 v[16];
+    u64 v1[1][16];  // one register set: the round helpers' Q = 1
+    u64(&v)[16] = v1[0];
     if (!INV) {
         const u64* tw = P.tw + (u64)t * N * 2;
 #pragma unroll
@@ -1375,13 +1279,13 @@ __global__ __launch_bounds__(512) void k_tcols9(PlanArgs P, const u64* src, u64*
             for (int k = 0; k < 16; k++) v[k] += other[L1 + 16 * W * k];
         }
         __syncthreads();  // the partner has read this half's slots
-        fwd_round16(v, tw, 2 + hf, M);
+        fwd_round16(v1, tw, 2 + hf, M);
 #pragma unroll
         for (int k = 0; k < 16; k++) my[L1 + 16 * W * k] = v[k];
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = my[L2 + W * k];
-        fwd_round16(v, tw, 32 + 16 * hf + h, M);
+        fwd_round16(v1, tw, 32 + 16 * hf + h, M);
 #pragma unroll
         for (int k = 0; k < 16; k++) st_s(y + (u64)(16 * h + k) * S + r, v[k]);
     } else {

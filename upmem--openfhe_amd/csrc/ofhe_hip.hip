@@ -562,29 +562,26 @@ static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, con
                     hipLaunchKernelGGL((k_tcols9<INV, SP>), dim3(nwg), dim3(512), 0, s, a, src, dst, batch, nwg);
                 }
             } else if (split != SPLIT_COLS) {
-                // the forward pass at N = 2^16 without a lift runs two columns per
-                // thread (16-byte accesses) when every row segment of src and dst
-                // is 16-byte aligned; any other call runs one column per thread
-                // and gives the same words
-                const bool aligned = split == SPLIT_T8 && !lift && !(((uintptr_t)src | (uintptr_t)dst) & 15) &&
-                                     !((a.sstride | a.dstride) & 1);
-                const bool pairs = TCOLS_CPT == 2 && !inv && aligned;
-                // so does the inverse pass (k_tcols_inv2), under the same conditions, at
-                // three workgroups per CU (TCOLS_INV_HOLD bytes of unused dynamic LDS)
-                if constexpr (INV && !SWS && TCOLS_CPT_INV == 2) {
-                    if (aligned) {
-                        const u32 nwg = polys * (256 / (2 * TCOLS_W));
-                        hipLaunchKernelGGL((k_tcols_inv2<SP>), dim3(nwg), dim3(16 * TCOLS_W), TCOLS_INV_HOLD, s, a, src,
-                                           dst, batch, nwg);
-                        return;
-                    }
-                }
+                // either pass at N = 2^16 without a lift runs two columns per thread
+                // (16-byte accesses) when every row segment of src and dst is 16-byte
+                // aligned and the direction's knob allows it; any other call runs one
+                // column per thread and gives the same words
+                constexpr int KNOB = INV ? TCOLS_CPT_INV : TCOLS_CPT;
+                const bool pairs = KNOB == 2 && split == SPLIT_T8 && !lift &&
+                                   !(((uintptr_t)src | (uintptr_t)dst) & 15) && !((a.sstride | a.dstride) & 1);
                 with_int<16, 17>(split == SPLIT_T8B9 ? 17 : 16, [&](auto ln) { with_bool(pairs, [&](auto pr) {
                     constexpr int LOGN = decltype(ln)::value;
-                    constexpr int CPT = (decltype(pr)::value && !INV && LOGN == 16 && !SWS) ? TCOLS_CPT : 1;
+                    constexpr int CPT = (decltype(pr)::value && LOGN == 16 && !SWS) ? KNOB : 1;
                     const u32 nwg = polys * ((1u << (LOGN - 8)) / (TCOLS_W * CPT));  // 256 or 512 columns
-                    hipLaunchKernelGGL((k_tcols<INV, SP, SWS, LOGN, CPT>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
-                                       src, dst, batch, nwg, S);
+                    if constexpr (INV && CPT == 2) {
+                        // the inverse's kernel of its own, at three workgroups per CU
+                        // (TCOLS_INV_HOLD bytes of unused dynamic LDS)
+                        hipLaunchKernelGGL((k_tcols_inv2<SP>), dim3(nwg), dim3(16 * TCOLS_W), TCOLS_INV_HOLD, s, a, src,
+                                           dst, batch, nwg);
+                    } else {
+                        hipLaunchKernelGGL((k_tcols<INV, SP, SWS, LOGN, CPT>), dim3(nwg), dim3(16 * TCOLS_W), 0, s, a,
+                                           src, dst, batch, nwg, S);
+                    }
                 }); });
             } else {
                 with_int<1, 2, 3, 4, 5>((int)a.log_n - 12, [&](auto ka) {
@@ -599,6 +596,14 @@ static void launch_colpass(const PlanArgs& a, bool spq, int split, bool inv, con
     }); }); });
 }
 
+// Work items of a block pass: one per 4096-element block (NR = 3), or per 1024
+// elements of QP quads of consecutive polynomials of a tower (NR = 2, block_body
+// and block_body_q2): the same count when batch % (4 QP) == 0.
+static u32 block_items(int NR, int QP, u32 batch, const PlanArgs& a) {
+    return NR == 2 ? ((batch + 4 * QP - 1) / (4 * QP)) * a.towers * (1u << (a.log_n - 10))
+                   : batch * a.towers * (1u << (a.log_n - 12));
+}
+
 // Pass split for log_n > 12 (the plan's split, internal.hpp): the block pass
 // runs the last 8 (SPLIT_T8 / T9: k_block NR = 2), 9 (SPLIT_T8B9: NR = 3
 // without the first three stages of its first round) or 12 stages.
@@ -607,15 +612,11 @@ static void launch_block(const PlanArgs& a, bool spq, const u64* src, u64* dst, 
                          hipStream_t s, int split = SPLIT_COLS) {
     with_bool(spq, [&](auto sp) { with_int<8, 9, 12>((int)block_stages(split, a.log_n), [&](auto st) {
         constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
-        // one work item per 4096-element block (NR = 3), or per 1024 elements
-        // of four consecutive polynomials of a tower (NR = 2, block_body): the
-        // same count when batch % 4 == 0.  The fused pipeline at N = 2^16 runs
-        // two such quads per thread (QP = 2: an octet of polynomials per item);
-        // the standalone modes and N = 2^17 keep one.
+        // The fused pipeline at N = 2^16 runs two quads of polynomials per thread
+        // (QP = 2: an octet per item); the standalone modes and N = 2^17 keep one.
         with_bool(NR == 2 && MODE == MODE_FUSED && a.log_n == 16, [&](auto oct) {
             constexpr int QP = (NR == 2 && MODE == MODE_FUSED && decltype(oct)::value) ? 2 : 1;
-            const u32 nwg = NR == 2 ? ((batch + 4 * QP - 1) / (4 * QP)) * a.towers * (1u << (a.log_n - 10))
-                                    : batch * a.towers * (1u << (a.log_n - 12));
+            const u32 nwg = block_items(NR, QP, batch, a);
             hipLaunchKernelGGL((k_block<MODE, decltype(sp)::value, NR, SK, QP>), dim3(nwg), dim3(256), 0, s, a, src,
                                dst, b, batch, nwg);
         });
@@ -627,8 +628,7 @@ static void launch_block_add(const PlanArgs& a, bool spq, const u64* src, u64* d
                              u32 batch, hipStream_t s, int split) {
     with_bool(spq, [&](auto sp) { with_int<8, 9, 12>((int)block_stages(split, a.log_n), [&](auto st) {
         constexpr int NR = decltype(st)::value == 8 ? 2 : 3, SK = decltype(st)::value == 9 ? 3 : 0;
-        const u32 nwg = NR == 2 ? ((batch + 3) / 4) * a.towers * (1u << (a.log_n - 10))
-                                : batch * a.towers * (1u << (a.log_n - 12));
+        const u32 nwg = block_items(NR, 1, batch, a);
         hipLaunchKernelGGL((k_block_add<decltype(sp)::value, NR, SK>), dim3(nwg), dim3(256), 0, s, a, src, dst, b, add,
                            batch, nwg);
     }); });
